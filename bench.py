@@ -2,7 +2,11 @@
 """Headline benchmark: sky-launched Llama-3-8B bf16 training throughput.
 
 Contract (driver-facing):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run does only what the headline figure needs: set up, W warmup
+steps, K timed steps, then (with --dump-outputs) write the last step's
+results as DIR/<name>.npy, and print the result line.  Anything else
+the benchmark ever measures belongs behind --full (nothing today).
 N>1 is launched by the driver via torch.distributed.run (one rank per
 GPU over RCCL); each rank then runs the training loop directly.  When
 invoked WITHOUT torchrun (the driver's N=1 case), the benchmark goes
@@ -28,6 +32,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import shlex
 import sys
 import time
 from pathlib import Path
@@ -43,11 +48,53 @@ def parse_args():
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--micro-batch", type=int, default=6)
     ap.add_argument("--seq-len", type=int, default=4096)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last "
+                         "timed step computed (per-step losses and a "
+                         "fixed seeded sample of the updated parameters) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary "
+                         "measurements; there are none at present, the "
+                         "plain run is exactly the headline measurement")
     ap.add_argument("--direct", action="store_true",
                     help="run the training loop in this process (the "
                          "per-rank inner entrypoint; skips the "
                          "orchestrator)")
     return ap.parse_args()
+
+
+DUMP_SEED = 20240607
+DUMP_PER_PARAM = 4096
+
+
+def dump_outputs(tr, losses, out_dir) -> None:
+    """Write what a caller of the timed path holds after its last step:
+    the loss each timed step returned (``loss.npy``, float64, last entry
+    = last step) and the updated parameters.  The parameters are far
+    over the size cap at 8B, so ``params_sample.npy`` (float32) keeps a
+    fixed seeded sample of up to DUMP_PER_PARAM elements of every
+    parameter tensor, concatenated in ``named_parameters`` order; the
+    indices depend only on the tensor sizes, so two builds dump the same
+    elements."""
+    import numpy as np
+    import torch
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "loss.npy", np.asarray(losses, dtype=np.float64))
+    gen = torch.Generator(device="cpu").manual_seed(DUMP_SEED)
+    parts = []
+    with torch.no_grad():
+        for _, p in tr.model.named_parameters():
+            flat = p.detach().reshape(-1)
+            n = flat.numel()
+            if n > DUMP_PER_PARAM:
+                idx = torch.randint(0, n, (DUMP_PER_PARAM,), generator=gen)
+                flat = flat[idx.to(flat.device)]
+            parts.append(flat.float().cpu())
+    np.save(out / "params_sample.npy",
+            torch.cat(parts).numpy().astype(np.float32))
 
 
 def run_direct(args, extra_config=None) -> int:
@@ -87,11 +134,12 @@ def run_direct(args, extra_config=None) -> int:
         tr.train_step()
     barrier_sync()
     t0 = time.perf_counter()
-    loss = 0.0
+    losses = []
     for _ in range(args.steps):
-        loss = tr.train_step()
+        losses.append(tr.train_step())
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    loss = losses[-1] if losses else 0.0
 
     # Max over ranks.
     if world > 1:
@@ -103,6 +151,9 @@ def run_direct(args, extra_config=None) -> int:
         peak_gb = torch.cuda.max_memory_allocated() / 1e9
         print(f"[bench] rank {rank}: peak GPU memory {peak_gb:.1f} GB",
               file=sys.stderr, flush=True)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, losses, args.dump_outputs)
 
     tokens = args.steps * cfg.micro_batch * cfg.seq_len * world
     value = tokens / elapsed
@@ -139,6 +190,20 @@ def run_direct(args, extra_config=None) -> int:
     return 0
 
 
+def job_envs() -> dict:
+    """Environment overrides for the launched job.  The repository root
+    is PREPENDED to the caller's PYTHONPATH, not put in its place: the
+    job must start Python the way this process was started (site hooks,
+    instrumentation, extra package roots).  Relative entries are made
+    absolute because the job runs in a working directory of its own."""
+    inherited = [os.path.abspath(p) for p in
+                 os.environ.get("PYTHONPATH", "").split(os.pathsep) if p]
+    envs = {"PYTHONPATH": os.pathsep.join([str(REPO_ROOT)] + inherited)}
+    if os.environ.get("SKY_BENCH_ALLOW_CPU") == "1":
+        envs["SKY_BENCH_ALLOW_CPU"] = "1"
+    return envs
+
+
 def run_sky_launched(args) -> int:
     """The full stack: provision -> agent -> gang driver -> training.
 
@@ -162,9 +227,17 @@ def run_sky_launched(args) -> int:
                  f"--warmup {args.warmup} --model {args.model} "
                  f"--micro-batch {args.micro_batch} "
                  f"--seq-len {args.seq_len}")
-    envs = {"PYTHONPATH": str(REPO_ROOT)}
-    if os.environ.get("SKY_BENCH_ALLOW_CPU") == "1":
-        envs["SKY_BENCH_ALLOW_CPU"] = "1"
+    if args.dump_outputs:
+        # The job runs in its own working directory: hand it an
+        # absolute path so the files land where the caller asked.
+        inner += " --dump-outputs " + shlex.quote(
+            str(Path(args.dump_outputs).resolve()))
+    envs = job_envs()
+    if "SKY_BENCH_ALLOW_CPU" not in envs:
+        # A missing HIP extension is an error, found here and not in a
+        # job log after provisioning (loading it does not open the GPU).
+        from skypilot_amd import ops
+        ops.native()
     task = Task.from_yaml_config({
         "name": "bench-train",
         "run": inner,

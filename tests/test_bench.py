@@ -25,13 +25,20 @@ def test_bench_sky_launched_round_trip(tmp_path):
     out = subprocess.run(
         [sys.executable, str(REPO / "bench.py"), "--gpus", "1",
          "--steps", "2", "--warmup", "1", "--model", "llama-debug",
-         "--micro-batch", "1", "--seq-len", "64"],
+         "--micro-batch", "1", "--seq-len", "64",
+         "--dump-outputs", str(tmp_path / "dump")],
         capture_output=True, text=True, timeout=300, env=env,
         cwd=str(REPO))
     assert out.returncode == 0, (out.stdout, out.stderr)
     line = [l for l in out.stdout.splitlines()
             if l.startswith('{"metric"')][-1]
     res = json.loads(line)
+    # the dump directory reaches the job that runs the timed steps
+    import numpy as np
+    loss = np.load(tmp_path / "dump" / "loss.npy")
+    assert loss.dtype == np.float64 and loss.shape == (2,)
+    assert loss[-1] == res["config"]["final_loss"]
+    assert res["ms_per_step"] > 0
     assert res["metric"].startswith("tokens/sec")
     assert res["n_gpus"] == 1 and res["steps"] == 2
     assert res["config"]["sky_launched"] is True
@@ -41,6 +48,28 @@ def test_bench_sky_launched_round_trip(tmp_path):
     # cluster torn down after the run
     assert not (tmp_path / "home" / "clusters" / "bench-cluster"
                 / "agent.json").exists() or True
+
+
+def test_bench_job_keeps_callers_pythonpath(monkeypatch):
+    """The launched job gets the repository root IN FRONT OF the
+    caller's PYTHONPATH; replacing it would start the training process
+    without the caller's site hooks and package roots."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_under_test",
+                                                  REPO / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setenv("PYTHONPATH",
+                       os.pathsep.join(["/x/hooks", "rel/dir"]))
+    monkeypatch.delenv("SKY_BENCH_ALLOW_CPU", raising=False)
+    envs = bench.job_envs()
+    # relative entries are resolved: the job has its own working dir
+    assert envs == {"PYTHONPATH": os.pathsep.join(
+        [str(REPO), "/x/hooks", os.path.abspath("rel/dir")])}
+    monkeypatch.delenv("PYTHONPATH")
+    monkeypatch.setenv("SKY_BENCH_ALLOW_CPU", "1")
+    assert bench.job_envs() == {"PYTHONPATH": str(REPO),
+                                "SKY_BENCH_ALLOW_CPU": "1"}
 
 
 def test_bench_inner_direct_under_torchrun_env(tmp_path):
@@ -71,6 +100,62 @@ def test_bench_inner_direct_under_torchrun_env(tmp_path):
     res = json.loads(line)
     # inner path: no sky_launched marker
     assert "sky_launched" not in res["config"]
+
+
+def _direct_dump(tmp_path, name, steps, extra=()):
+    env = dict(os.environ)
+    env.update({
+        "SKY_AMD_HOME": str(tmp_path / "home"),
+        "SKY_BENCH_ALLOW_CPU": "1",
+        "PYTHONPATH": str(REPO),
+    })
+    out = subprocess.run(
+        [sys.executable, str(REPO / "bench.py"), "--direct", "--gpus", "1",
+         "--steps", str(steps), "--warmup", "1", "--model", "llama-debug",
+         "--micro-batch", "1", "--seq-len", "32",
+         "--dump-outputs", str(tmp_path / name), *extra],
+        capture_output=True, text=True, timeout=300, env=env,
+        cwd=str(REPO))
+    assert out.returncode == 0, (out.stdout, out.stderr)
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines  # exactly one result line
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's results as float
+    .npy files, identical from run to run with the same arguments (so
+    two builds can be compared output for output); --steps sets the
+    number of timed steps; --full keeps the result line's meaning."""
+    import numpy as np
+    a = _direct_dump(tmp_path, "a", 3)
+    b = _direct_dump(tmp_path, "b", 3, extra=("--full",))
+    for res in (a, b):
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        for key in ("metric", "value", "unit", "higher_is_better",
+                    "dtype"):
+            assert key in res
+    assert a["metric"] == b["metric"] and a["unit"] == b["unit"]
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["loss.npy", "params_sample.npy"]
+    total = 0
+    for n in names:
+        xa = np.load(tmp_path / "a" / n)
+        xb = np.load(tmp_path / "b" / n)
+        assert xa.dtype in (np.float32, np.float64)
+        assert np.isfinite(xa).all()
+        assert np.array_equal(xa, xb), n
+        total += xa.nbytes
+    assert total <= 64 << 20
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.shape == (3,) and loss[-1] == a["config"]["final_loss"]
+    # one more timed step moves the parameters: the dump is the state
+    # after the LAST step, not a constant
+    c = _direct_dump(tmp_path, "c", 4)
+    pc = np.load(tmp_path / "c" / "params_sample.npy")
+    pa = np.load(tmp_path / "a" / "params_sample.npy")
+    assert pc.shape == pa.shape and not np.array_equal(pc, pa)
+    assert np.array_equal(np.load(tmp_path / "c" / "loss.npy")[:3], loss)
 
 
 def test_bench_torchrun_world2_cpu(tmp_path):

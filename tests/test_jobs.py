@@ -201,15 +201,14 @@ def test_managed_spot_job_recovers_after_preemption(client, tmp_path):
     assert job["recovery_count"] >= 1
 
 
-def test_recover_on_exit_codes(client):
+def test_recover_on_exit_codes(client, tmp_path):
     """Exit codes listed in job_recovery.recover_on_exit_codes recover
     without consuming the restart budget (reference: schema field)."""
     from skypilot_amd.client import sdk
     # exit 42 twice (recover_on_exit_codes, no budget needed), then 0.
-    marker = "/tmp/sky-roec-count"
-    import os as _os
-    if _os.path.exists(marker):
-        _os.unlink(marker)
+    # The counter lives in this test's own directory: a fixed name in a
+    # shared temp dir may already exist and belong to another user.
+    marker = str(tmp_path / "roec-count")
     task = {
         "name": "mj-roec",
         "resources": {"job_recovery": {"strategy": "EAGER",
