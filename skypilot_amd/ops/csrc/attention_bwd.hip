@@ -23,22 +23,26 @@
 // ---------------------------------------------------------------------------
 extern "C" __global__ void attn_bwd_pre_kernel(
     const unsigned short* __restrict__ dO, const unsigned short* __restrict__ O,
-    float* __restrict__ Dvec, long long rows, int Hq) {
-  (void)Hq;
+    float* __restrict__ Dvec, long long rows, int S, int Hq) {
   const int lane = threadIdx.x & 63;
   const long long wave_id =
       (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const long long stride = (long long)gridDim.x * (blockDim.x >> 6);
   for (long long row = wave_id; row < rows; row += stride) {
-    // row = (b*S + s)*Hq + h ; layout [B,S,Hq,D] is contiguous in rows*D.
+    // row = (b*S + s)*Hq + h ; layout [B,S,Hq,D] is contiguous in rows*D,
+    // so consecutive waves keep reading consecutive 256 B rows.
     const unsigned short* drow = dO + row * ATT_D;
     const unsigned short* orow = O + row * ATT_D;
     float acc = bf2f(drow[lane]) * bf2f(orow[lane]) +
                 bf2f(drow[lane + 64]) * bf2f(orow[lane + 64]);
     acc = wave_reduce_sum(acc);
-    // Dvec is stored [B,S,Hq] (same row order as the [B,S,Hq,D] tensors);
-    // the dkv/dq kernels index it with stride Hq accordingly.
-    if (lane == 0) Dvec[row] = acc;
+    // Dvec is stored [B,Hq,S], the layout lse has: contiguous in s, so
+    // the dkv/dq kernels read a lane's runs of q rows as float4.
+    const int hh = (int)(row % Hq);
+    const long long bs = row / Hq;
+    const int ss = (int)(bs % S);
+    const long long bb = bs / S;
+    if (lane == 0) Dvec[(bb * Hq + hh) * S + ss] = acc;
   }
 }
 
@@ -103,8 +107,8 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
     const unsigned short* Qb = Q + ((long long)b * S * Hq + qh) * ATT_D;
     const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
     const float* lse_b = lse + ((long long)b * Hq + qh) * S;
-    // Dvec stored [B,S,Hq] (see pre kernel).
-    const float* dvec_b = Dvec + (long long)b * S * Hq + qh;
+    // Dvec stored [B,Hq,S] like lse (see pre kernel).
+    const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
 
     const int qt0 = causal ? kvbase / BM : 0;
     for (int qt = qt0; qt < S / BM; ++qt) {
@@ -161,7 +165,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_kernel(
       for (int ct = 0; ct < 4; ++ct) {
         int qcol = qbase + ct * 16 + lrow;
         float l = lse_b[qcol];
-        float dv = dvec_b[(long long)qcol * Hq];
+        float dv = dvec_b[qcol];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float sv = st[ct][r] * scale;
@@ -252,7 +256,7 @@ extern "C" __global__ __launch_bounds__(256, 1) void attn_bwd_dq_kernel(
   const unsigned short* Vb = V + ((long long)b * S * Hkv + kvh) * ATT_D;
   const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
   const float* lse_b = lse + ((long long)b * Hq + qh) * S;
-  const float* dvec_b = Dvec + (long long)b * S * Hq + qh;
+  const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
 
   // Fixed A fragments: Q rows and dO rows for this wave.
   s16x8 a_q[4], a_do[4];
@@ -270,7 +274,7 @@ extern "C" __global__ __launch_bounds__(256, 1) void attn_bwd_dq_kernel(
     for (int r = 0; r < 4; ++r) {
       int rr = qbase + 16 * w + lgrp * 4 + r;
       my_lse[r] = lse_b[rr];
-      my_dvec[r] = dvec_b[(long long)rr * Hq];
+      my_dvec[r] = dvec_b[rr];
     }
   }
 
@@ -442,7 +446,7 @@ extern "C" __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel32(
     const unsigned short* dOb =
         dO + ((long long)b * S * Hq + qh_head) * ATT_D;
     const float* lse_b = lse + ((long long)b * Hq + qh_head) * S;
-    const float* dvec_b = Dvec + (long long)b * S * Hq + qh_head;
+    const float* dvec_b = Dvec + ((long long)b * Hq + qh_head) * S;
 
     const int qt0 = causal ? kvbase / BM : 0;
     for (int qt = qt0; qt < S / BM; ++qt) {
@@ -511,7 +515,7 @@ extern "C" __global__ __launch_bounds__(512, 2) void attn_bwd_dkv_kernel32(
       if (!is_st) {
         // dST = PT * (dPT - Dvec[q]) -> ds_lds (reads PT written above).
         const int qcol = qbase + t_qh * 32 + col;
-        const float dvq = dvec_b[(long long)qcol * Hq];
+        const float dvq = dvec_b[qcol];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           int kvrow = t_kvh * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
@@ -575,7 +579,8 @@ extern "C" void attn_bwd_v3_launch(const void* Q, const void* K,
                                    const float* lse, const float* Dvec,
                                    void* dQ, void* dK, void* dV, int B,
                                    int S, int Hq, int Hkv, float scale,
-                                   bool causal, hipStream_t stream);
+                                   bool causal, int dkv_variant,
+                                   hipStream_t stream);
 
 extern "C" __global__ void attn_bwd_dkv_swapped_kernel(
     const unsigned short*, const unsigned short*, const unsigned short*,
@@ -592,20 +597,22 @@ extern "C" void attn_bwd_launch(const void* Q, const void* K, const void* V,
                                 const float* lse, float* Dvec, void* dQ,
                                 void* dK, void* dV, int B, int S, int Hq,
                                 int Hkv, float scale, bool causal,
-                                hipStream_t stream) {
+                                int dkv_variant, hipStream_t stream) {
   long long rows = (long long)B * S * Hq;
   hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3(membound_grid(rows, 4)),
                      dim3(256), 0, stream, (const unsigned short*)dO,
-                     (const unsigned short*)O, Dvec, rows, Hq);
+                     (const unsigned short*)O, Dvec, rows, S, Hq);
   // v3 (32x32 deep-pipelined dkv/dq) is the round-2 default for the
   // flagship shapes; SKY_ATTN_BWD_V3=0 for A/B.
   static const int use_bwd_v3 = [] {
     const char* e = getenv("SKY_ATTN_BWD_V3");
     return e ? atoi(e) : 1;
   }();
-  if (use_bwd_v3 && S % 128 == 0) {
+  // dkv_variant >= 0 picks a v3 dkv kernel explicitly (in-process A/B,
+  // see attn_bwd_v3_launch); -1 leaves the choice to the environment.
+  if ((use_bwd_v3 || dkv_variant >= 0) && S % 128 == 0) {
     attn_bwd_v3_launch(Q, K, V, dO, lse, Dvec, dQ, dK, dV, B, S, Hq, Hkv,
-                       scale, causal, stream);
+                       scale, causal, dkv_variant, stream);
     return;
   }
   // NOTE: attn_bwd_dkv_kernel32 (8-wave 32x32, half the instructions)
@@ -704,7 +711,7 @@ extern "C" __global__ __launch_bounds__(256, 1) void attn_bwd_dq_swapped_kernel(
   const unsigned short* Vb = V + ((long long)b * S * Hkv + kvh) * ATT_D;
   const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
   const float* lse_b = lse + ((long long)b * Hq + qh) * S;
-  const float* dvec_b = Dvec + (long long)b * S * Hq + qh;
+  const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
 
   // Q / dO as B-fragments (byte-identical loads to the A-fragments of
   // the unswapped kernel); lse/D collapse to per-lane scalars.
@@ -720,7 +727,7 @@ extern "C" __global__ __launch_bounds__(256, 1) void attn_bwd_dq_swapped_kernel(
     }
   }
   const float my_lse = lse_b[my_q];
-  const float my_dvec = dvec_b[(long long)my_q * Hq];
+  const float my_dvec = dvec_b[my_q];
 
   f32x4 dq_t[8];  // dQ^T: C[row=d=ct*16+lgrp*4+r][col=q=lrow]
 #pragma unroll
@@ -881,7 +888,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_swapped_kernel
     const unsigned short* Qb = Q + ((long long)b * S * Hq + qh) * ATT_D;
     const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
     const float* lse_b = lse + ((long long)b * Hq + qh) * S;
-    const float* dvec_b = Dvec + (long long)b * S * Hq + qh;
+    const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
 
     const int qt0 = causal ? kvbase / BM : 0;
     for (int qt = qt0; qt < S / BM; ++qt) {
@@ -936,7 +943,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_swapped_kernel
       for (int qsub = 0; qsub < 4; ++qsub) {
         int qc = qbase + qsub * 16 + lrow;
         lse_l[qsub] = lse_b[qc];
-        dv_l[qsub] = dvec_b[(long long)qc * Hq];
+        dv_l[qsub] = dvec_b[qc];
       }
 #pragma unroll
       for (int qsub = 0; qsub < 4; ++qsub)
@@ -1072,7 +1079,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_tr_kernel(
     const unsigned short* Qb = Q + ((long long)b * S * Hq + qh) * ATT_D;
     const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
     const float* lse_b = lse + ((long long)b * Hq + qh) * S;
-    const float* dvec_b = Dvec + (long long)b * S * Hq + qh;
+    const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
 
     const int qt0 = causal ? kvbase / BM : 0;
     for (int qt = qt0; qt < S / BM; ++qt) {
@@ -1113,7 +1120,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_tr_kernel(
       for (int ct = 0; ct < 4; ++ct) {
         int qcol = qbase + ct * 16 + lrow;
         float l = lse_b[qcol];
-        float dvv = dvec_b[(long long)qcol * Hq];
+        float dvv = dvec_b[qcol];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float sv = st[ct][r] * scale;

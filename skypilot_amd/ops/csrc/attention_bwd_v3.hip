@@ -115,7 +115,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_v3_kernel(
     const unsigned short* Qb = Q + ((long long)b * S * Hq + qh) * ATT_D;
     const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
     const float* lse_b = lse + ((long long)b * Hq + qh) * S;
-    const float* dvec_b = Dvec + (long long)b * S * Hq + qh;
+    const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
 
     for (int qt = qt0; qt < n_qt; ++qt) {
       const int qbase = qt * 32;
@@ -175,7 +175,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_v3_kernel(
         float p = exp2f(st[r] - l2);
         if (need_mask && qbase + ql < my_kv) p = 0.f;
         st[r] = p;
-        dpt[r] = p * (dpt[r] - dvec_b[(long long)(qbase + ql) * Hq]);
+        dpt[r] = p * (dpt[r] - dvec_b[qbase + ql]);
       }
 
       // ---- dV += P^T dO ; dK += dS^T Q.  A-fragments come straight
@@ -256,6 +256,310 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_v3_kernel(
   }
 }
 
+// A wave-uniform pointer pinned to scalar registers: loads through
+// `uniform_ptr(p) + lane_offset32` take the scalar-base + 32-bit
+// lane-offset form and need no 64-bit per-lane address registers.
+typedef const __attribute__((address_space(1))) char* gptr_t;
+__device__ __forceinline__ gptr_t uniform_ptr(const void* p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (gptr_t)(((unsigned long long)hi << 32) | lo);
+}
+typedef const __attribute__((address_space(1))) s16x8* g_s16x8_t;
+typedef const __attribute__((address_space(1))) f32x4* g_f32x4_t;
+
+// ---------------------------------------------------------------------------
+// Pipelined dkv kernel: the same MFMA sequence, LDS layouts and
+// accumulation order as attn_bwd_dkv_v3_kernel (dK/dV are bit-identical);
+// only the schedule of the memory traffic differs.
+//
+//  * Q/dO staging is split into a global->register load and a
+//    register->LDS write one iteration apart: the loads of tile t+1 are
+//    issued right after the second barrier of tile t (4 x 16 B per
+//    thread, 16 VGPRs) and land during tile t's MFMAs; the ds_write runs
+//    at the top of iteration t+1 after the first barrier.  The prefetch
+//    crosses the q-head boundary; a prologue loads the first tile.  LDS
+//    stays at 80 KB.
+//  * lse and Dvec ([B,Hq,S], contiguous in s) come in as 4 + 4 float4
+//    loads per lane, issued before the first barrier and consumed after
+//    the S/dP MFMA chain.  They are issued BEFORE the tile prefetch so
+//    that the counted vmcnt wait in front of the softmax leaves the four
+//    prefetch loads in flight.
+//  * heavy_first swaps the grid axes (grid = (B*Hkv, S/128)): blocks are
+//    dispatched in descending causal work order, kt = 0 of every
+//    (b, kv-head) first.
+//
+// Every wave still reaches both barriers of every iteration; the causal
+// skip drops only compute (a skipping wave still stages and prefetches).
+// ---------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dkv_v3p_kernel(
+    const unsigned short* __restrict__ Q, const unsigned short* __restrict__ K,
+    const unsigned short* __restrict__ V, const unsigned short* __restrict__ dO,
+    const float* __restrict__ lse, const float* __restrict__ Dvec,
+    unsigned short* __restrict__ dK, unsigned short* __restrict__ dV, int B,
+    int S, int Hq, int Hkv, float scale, int causal, int heavy_first) {
+  // One array so every tile sits at a compile-time offset from the
+  // others (tr reads of do_lds and of the second 16 q rows then reuse
+  // the q_lds address registers through the DS offset field).  The tiles
+  // and their internal layouts are those of attn_bwd_dkv_v3_kernel.
+  // 80 KB total: exactly two blocks per CU — no second Q/dO buffer.
+  __shared__ unsigned short lds[(2 * 32 + 2 * 128) * ATT_D];
+  unsigned short* q_lds = lds;                    // 8 KB, swzK16 layout
+  unsigned short* do_lds = lds + 32 * ATT_D;      // 8 KB
+  unsigned short* k_own = lds + 64 * ATT_D;       // 32 KB, block's K rows
+  unsigned short* v_own = lds + 192 * ATT_D;      // 32 KB, block's V rows
+
+  const int kt = heavy_first ? blockIdx.y : blockIdx.x;
+  const int bh = heavy_first ? blockIdx.x : blockIdx.y;
+  const int b = bh / Hkv;
+  const int kvh = bh % Hkv;
+  const int group = Hq / Hkv;
+  const int kvb = kt * 128;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int col = lane & 31;
+  const int h = lane >> 5;
+  const int g = lane >> 4;
+  const int lw = lane & 15;
+
+  const long long q_rowstride = (long long)Hq * ATT_D;
+  const long long kv_rowstride = (long long)Hkv * ATT_D;
+  const unsigned short* Kb = K + ((long long)b * S * Hkv + kvh) * ATT_D;
+  const unsigned short* Vb = V + ((long long)b * S * Hkv + kvh) * ATT_D;
+
+  const int my_kv = kvb + 32 * w + col;
+
+  const int qt0 = causal ? kvb / 32 : 0;
+  const int n_qt = S / 32;
+
+  // The eight tr-read addresses of q rows 0..15 in q_lds (DKV_TR_ISSUE
+  // with ks = 0); the other three fragment sets are constant offsets.
+  unsigned tra[8];
+  {
+    const int q_s = ((g >> 1) << 3) + (lw >> 2);
+    const int d_s = ((g & 1) << 4) + ((lw & 3) << 2);
+    const unsigned base = (unsigned)(size_t)((char*)q_lds);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      tra[i] = DKV_TRA(base, q_s + 4 * (i & 1), 32 * (i >> 1) + d_s);
+  }
+#define DKVP_TR_ISSUE(off)                                                \
+  {                                                                       \
+    ds_tr4_issue_off<(off)>(&t0, tra[0], tra[1], tra[2], tra[3]);         \
+    ds_tr4_issue_off<(off)>(&t1, tra[4], tra[5], tra[6], tra[7]);         \
+  }
+
+  // Row-fragment byte offsets at k-step 0: swzK16(col*256 + h*16, col) in
+  // the Q/dO tile and the same for row 32w+col of K/V.  k-step ks sits at
+  // offset ^ (ks << 5): (2ks + h) ^ x == (h ^ x) ^ 2ks, and neither the
+  // row term (bits >= 8) nor 8192w touches bits 5..7.
+  const unsigned frag_q = (unsigned)swzK16(col * 256 + h * 16, col);
+  const unsigned frag_k = frag_q + (unsigned)w * 8192u;
+
+  // Prefetch registers for the next Q/dO tile (2 x 16 B chunks each).
+  s16x8 pq[2], pd[2];
+  // Per-lane byte offset of this thread's two adjacent 16 B chunks inside
+  // a Q/dO tile; the tile base is wave-uniform (scalar base + 32-bit lane
+  // offset addressing keeps the loads off 64-bit address registers).
+  const unsigned st_off =
+      (unsigned)(((tid * 2) >> 4) * q_rowstride + ((tid * 2) & 15) * 8) * 2u;
+  const unsigned row_off = (unsigned)h * 16u;  // lse/Dvec: 4 floats per half
+#define DKVP_PREFETCH(qh_, qbase_)                                        \
+  {                                                                       \
+    const long long tb = ((long long)b * S * Hq + (qh_)) * ATT_D +        \
+                         (long long)(qbase_) * q_rowstride;               \
+    gptr_t qsrc = uniform_ptr(Q + tb) + st_off;                           \
+    gptr_t dsrc = uniform_ptr(dO + tb) + st_off;                          \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                       \
+      pq[i] = *(g_s16x8_t)(qsrc + 16 * i);                                \
+      pd[i] = *(g_s16x8_t)(dsrc + 16 * i);                                \
+    }                                                                     \
+  }
+  // Prologue: first tile of the first q head, in flight during the K/V
+  // staging below.
+  DKVP_PREFETCH(kvh * group, qt0 * 32);
+
+  // Block's K/V rows staged ONCE into LDS, K pre-scaled by
+  // scale*log2(e) (see attn_bwd_dkv_v3_kernel).
+  const float ksc = scale * 1.44269504088896340736f;
+  {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      int c = tid * 8 + i;  // 2048 16B chunks in a [128][128] tile
+      int kr = c >> 4;
+      int dch = (c & 15) * 8;
+      long long src = (long long)(kvb + kr) * kv_rowstride + dch;
+      s16x8 raw = *(const s16x8*)(Kb + src);
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        raw[j] = (short)f2bf(bf2f((unsigned short)raw[j]) * ksc);
+      int koff = kr * 256 + (((dch >> 3) ^ (kr & 15)) << 4);
+      *(s16x8*)((char*)k_own + koff) = raw;
+      *(s16x8*)((char*)v_own + koff) = *(const s16x8*)(Vb + src);
+    }
+  }
+
+  f32x16 dv_acc[4], dk_acc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      dv_acc[dt][r] = 0.f;
+      dk_acc[dt][r] = 0.f;
+    }
+
+  for (int gi = 0; gi < group; ++gi) {
+    const int qh = kvh * group + gi;
+    const float* lse_b = lse + ((long long)b * Hq + qh) * S;
+    const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
+
+    for (int qt = qt0; qt < n_qt; ++qt) {
+      const int qbase = qt * 32;
+      // ---- lse/Dvec rows of this lane: ql = (r&3) + 8(r>>2) + 4h is
+      // four runs of four consecutive q rows -> 4 + 4 float4 loads.
+      f32x4 lv4[4], dv4[4];
+      gptr_t lse_t = uniform_ptr(lse_b + qbase);
+      gptr_t dvec_t = uniform_ptr(dvec_b + qbase);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        lv4[j] = *(g_f32x4_t)(lse_t + 32 * j + row_off);
+        dv4[j] = *(g_f32x4_t)(dvec_t + 32 * j + row_off);
+      }
+      __syncthreads();
+      // ---- write the prefetched Q/dO tile to LDS.
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        int c = tid * 2 + i;
+        int qr = c >> 4;
+        int dch = (c & 15) * 8;
+        int off = qr * 256 + (((dch >> 3) ^ (qr & 15)) << 4);
+        *(s16x8*)((char*)q_lds + off) = pq[i];
+        *(s16x8*)((char*)do_lds + off) = pd[i];
+      }
+      __syncthreads();
+      // ---- issue the next tile's loads (next q tile, or the first tile
+      // of the next q head); they complete under this tile's MFMAs.  The
+      // loads are unconditional so that the wait in front of the softmax
+      // can be a counted vmcnt(4) on every path: the block's last
+      // iteration re-reads its own tile (16 KB, unused) instead.
+      {
+        int nqt = qt + 1, ngi = gi;
+        if (nqt == n_qt) {
+          nqt = qt0;
+          ngi = gi + 1;
+        }
+        if (ngi == group) {
+          nqt = qt;
+          ngi = gi;
+        }
+        DKVP_PREFETCH(kvh * group + ngi, nqt * 32);
+      }
+      // causal: this wave's kv rows see q tiles >= its diagonal only.
+      if (causal && qbase + 31 < kvb + 32 * w) {
+        // Name the lse/Dvec values on this path too: with a use on both
+        // paths the loads stay above the barriers, ahead of the prefetch
+        // in the vmcnt queue, instead of being sunk into the compute path.
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          asm volatile("" ::"v"(lv4[j]), "v"(dv4[j]));
+        continue;
+      }
+
+      // ---- S[q][kv_own] and dP[q][kv_own] (two interleaved chains).
+      f32x16 st, dpt;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        st[r] = 0.f;
+        dpt[r] = 0.f;
+      }
+      // Fragment addresses are rebuilt per k-step from two lane bases by
+      // one XOR each (frag_q/frag_k above) instead of being kept in 16
+      // loop-invariant registers; the empty asm makes the bases opaque
+      // per iteration so that they are not hoisted back out.
+      unsigned fq = frag_q, fk = frag_k;
+      asm volatile("" : "+v"(fq), "+v"(fk));
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        const unsigned oq = fq ^ (ks << 5), ok = fk ^ (ks << 5);
+        s16x8 aq = *(const s16x8*)((char*)q_lds + oq);
+        s16x8 kfr = *(const s16x8*)((char*)k_own + ok);
+        st = MFMA32V3(as_bf16x8(aq), as_bf16x8(kfr), st);
+        s16x8 ad = *(const s16x8*)((char*)do_lds + oq);
+        s16x8 vfr = *(const s16x8*)((char*)v_own + ok);
+        dpt = MFMA32V3(as_bf16x8(ad), as_bf16x8(vfr), dpt);
+      }
+      // Pin the interleave: two fragment pairs are read ahead, then each
+      // MFMA is followed by the reads of the pair two MFMAs later, so a
+      // read always has one full MFMA to land (three 8-register pairs).
+      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);  // 4 DS reads
+#pragma unroll
+      for (int i = 0; i < 14; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
+        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // 2 DS reads
+      }
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_s_setprio(0);
+
+      // ---- P = exp2(S' - lse'); dS = P * (dP - Dvec): the same guard,
+      // scaling and mask as attn_bwd_dkv_v3_kernel.
+      const bool need_mask = causal && qbase < kvb + 128;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ql = (r & 3) + ((r >> 2) << 3) + (h << 2);
+        float lv = lv4[r >> 2][r & 3];
+        float l2 = (lv == -INFINITY) ? 3.0e37f
+                                     : lv * 1.44269504088896340736f;
+        float p = exp2f(st[r] - l2);
+        if (need_mask && qbase + ql < my_kv) p = 0.f;
+        st[r] = p;
+        dpt[r] = p * (dpt[r] - dv4[r >> 2][r & 3]);
+      }
+
+      // ---- dV += P^T dO ; dK += dS^T Q (as attn_bwd_dkv_v3_kernel).
+      s16x8 pa, da;
+      tr4 t0, t1;
+      // tile byte offsets: do_lds = q_lds + 8192; q rows 16..31 = +4096.
+      DKVP_TR_ISSUE(8192);
+      V3_PACK1(pa, st, 0);
+      lgkm_wait0_bind2(&t0, &t1);
+      DKV_MFMA(dv_acc, pa);
+      DKVP_TR_ISSUE(8192 + 4096);
+      V3_PACK1(pa, st, 1);
+      lgkm_wait0_bind2(&t0, &t1);
+      DKV_MFMA(dv_acc, pa);
+      DKVP_TR_ISSUE(0);
+      V3_PACK1(da, dpt, 0);
+      lgkm_wait0_bind2(&t0, &t1);
+      DKV_MFMA(dk_acc, da);
+      DKVP_TR_ISSUE(4096);
+      V3_PACK1(da, dpt, 1);
+      lgkm_wait0_bind2(&t0, &t1);
+      DKV_MFMA(dk_acc, da);
+    }
+  }
+#undef DKVP_PREFETCH
+#undef DKVP_TR_ISSUE
+
+  // ---- epilogue: C-layout [kv row][d col]; dK gets the outer scale.
+  unsigned short* dKb = dK + ((long long)b * S * Hkv + kvh) * ATT_D;
+  unsigned short* dVb = dV + ((long long)b * S * Hkv + kvh) * ATT_D;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int kvrow = kvb + 32 * w + (r & 3) + ((r >> 2) << 3) + (h << 2);
+    unsigned short* krow = dKb + (long long)kvrow * kv_rowstride;
+    unsigned short* vrow = dVb + (long long)kvrow * kv_rowstride;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      krow[dt * 32 + col] = f2bf(dk_acc[dt][r] * scale);
+      vrow[dt * 32 + col] = f2bf(dv_acc[dt][r]);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // dq kernel.  Grid: (S/128, B*Hq); 256 threads (4 waves); wave w owns q
 // rows [qb+32w, qb+32w+32).  kv tiles of 64 staged by global_load_lds
@@ -318,7 +622,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dq_v3_kernel(
     float lv = lse[((long long)b * Hq + qh) * S + my_q];                  \
     lse2 = (lv == -INFINITY) ? 3.0e37f                                    \
                              : lv * 1.44269504088896340736f;              \
-    dvq = Dvec[((long long)b * S + my_q) * Hq + qh];                      \
+    dvq = Dvec[((long long)b * Hq + qh) * S + my_q];                      \
   }
   DQ_LOAD_Q();
   const unsigned short* do_src = dOb + (long long)my_q * q_rowstride;
@@ -513,18 +817,41 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dq_v3_kernel(
 #undef DQ_LOAD_Q
 }
 
+// dkv_variant: 0 = attn_bwd_dkv_v3_kernel, 1 = the pipelined kernel,
+// 2 = the pipelined kernel on the heavy-first grid; -1 = SKY_ATTN_DKV_PIPE
+// (same values) if set, else 2.  Measured per call at B6 S4096 Hq32 Hkv8
+// causal: 4.13 / 3.62 / 2.14 ms (docs/BENCHMARKS.md).
 extern "C" void attn_bwd_v3_launch(const void* Q, const void* K,
                                    const void* V, const void* dO,
                                    const float* lse, const float* Dvec,
                                    void* dQ, void* dK, void* dV, int B,
                                    int S, int Hq, int Hkv, float scale,
-                                   bool causal, hipStream_t stream) {
-  dim3 gkv(S / 128, B * Hkv);
-  hipLaunchKernelGGL(attn_bwd_dkv_v3_kernel, gkv, dim3(256), 0, stream,
-                     (const unsigned short*)Q, (const unsigned short*)K,
-                     (const unsigned short*)V, (const unsigned short*)dO,
-                     lse, Dvec, (unsigned short*)dK, (unsigned short*)dV, B,
-                     S, Hq, Hkv, scale, causal ? 1 : 0);
+                                   bool causal, int dkv_variant,
+                                   hipStream_t stream) {
+  static const int dkv_env = [] {
+    const char* e = getenv("SKY_ATTN_DKV_PIPE");
+    const int v = e ? atoi(e) : 2;
+    return v < 0 || v > 2 ? 2 : v;
+  }();
+  const int variant = dkv_variant >= 0 ? dkv_variant : dkv_env;
+  if (variant == 0) {
+    dim3 gkv(S / 128, B * Hkv);
+    hipLaunchKernelGGL(attn_bwd_dkv_v3_kernel, gkv, dim3(256), 0, stream,
+                       (const unsigned short*)Q, (const unsigned short*)K,
+                       (const unsigned short*)V, (const unsigned short*)dO,
+                       lse, Dvec, (unsigned short*)dK, (unsigned short*)dV,
+                       B, S, Hq, Hkv, scale, causal ? 1 : 0);
+  } else {
+    // heavy-first: x (fastest dispatched) runs over (b, kv-head), y over
+    // the kv tile, so all kt = 0 blocks start before any kt = 1 block.
+    const int heavy_first = variant == 2 ? 1 : 0;
+    dim3 gkv = heavy_first ? dim3(B * Hkv, S / 128) : dim3(S / 128, B * Hkv);
+    hipLaunchKernelGGL(attn_bwd_dkv_v3p_kernel, gkv, dim3(256), 0, stream,
+                       (const unsigned short*)Q, (const unsigned short*)K,
+                       (const unsigned short*)V, (const unsigned short*)dO,
+                       lse, Dvec, (unsigned short*)dK, (unsigned short*)dV,
+                       B, S, Hq, Hkv, scale, causal ? 1 : 0, heavy_first);
+  }
   int nqq = S / 128;
   int gqx = (causal && nqq % 2 == 0) ? nqq / 2 : nqq;
   dim3 gq(gqx, B * Hq);

@@ -72,6 +72,24 @@ __device__ __forceinline__ void lgkm_wait0_bind2(tr4* a, tr4* b) {
   __builtin_amdgcn_sched_barrier(0);
 }
 
+// ds_tr4_issue with a compile-time byte offset shared by the four reads
+// (the DS offset field): tiles a constant distance apart in LDS reuse
+// one set of address registers instead of holding a set per tile.
+template <int OFF>
+__device__ __forceinline__ void ds_tr4_issue_off(tr4* t, unsigned a0,
+                                                 unsigned a1, unsigned a2,
+                                                 unsigned a3) {
+  static_assert(OFF >= 0 && OFF < 65536, "DS offset field is 16 bits");
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %4 offset:%8\n\t"
+      "ds_read_b64_tr_b16 %1, %5 offset:%8\n\t"
+      "ds_read_b64_tr_b16 %2, %6 offset:%8\n\t"
+      "ds_read_b64_tr_b16 %3, %7 offset:%8"
+      : "=v"(t->d[0]), "=v"(t->d[1]), "=v"(t->d[2]), "=v"(t->d[3])
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "n"(OFF)
+      : "memory");
+}
+
 // Async 16B global->LDS copy: per-lane global source, wave-uniform LDS
 // base + lane*16 destination (guide §5: the only supported dest form).
 __device__ __forceinline__ void gload_lds16(const void* g, void* l) {

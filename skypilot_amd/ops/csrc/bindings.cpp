@@ -35,7 +35,7 @@ void attn_fwd_launch(const void*, const void*, const void*, void*, float*,
                      int, int, int, int, float, bool, hipStream_t);
 void attn_bwd_launch(const void*, const void*, const void*, const void*,
                      const void*, const float*, float*, void*, void*, void*,
-                     int, int, int, int, float, bool, hipStream_t);
+                     int, int, int, int, float, bool, int, hipStream_t);
 void mfma_probe_launch(const void*, const void*, float*, hipStream_t);
 void mfma32_probe_launch(const void*, const void*, float*, hipStream_t);
 void trb16_probe_launch(float*, int, hipStream_t);
@@ -178,8 +178,13 @@ std::vector<torch::Tensor> attn_fwd(torch::Tensor Q, torch::Tensor K,
 std::vector<torch::Tensor> attn_bwd(torch::Tensor Q, torch::Tensor K,
                                     torch::Tensor V, torch::Tensor O,
                                     torch::Tensor dO, torch::Tensor lse,
-                                    double scale, bool causal) {
+                                    double scale, bool causal,
+                                    int64_t dkv_variant) {
+  // dkv_variant: -1 = default (environment, else the shipped kernel);
+  // 0 = v3 dkv, 1 = pipelined v3 dkv, 2 = pipelined + heavy-first grid.
   CHECK_GPU(Q); CHECK_CONTIG(dO);
+  TORCH_CHECK(dkv_variant >= -1 && dkv_variant <= 2,
+              "attn_bwd: dkv_variant must be -1, 0, 1 or 2");
   const int B = (int)Q.size(0), S = (int)Q.size(1), Hq = (int)Q.size(2);
   const int Hkv = (int)K.size(2);
   auto dQ = torch::empty_like(Q);
@@ -190,7 +195,7 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor Q, torch::Tensor K,
                   dO.data_ptr(), lse.data_ptr<float>(),
                   Dvec.data_ptr<float>(), dQ.data_ptr(), dK.data_ptr(),
                   dV.data_ptr(), B, S, Hq, Hkv, (float)scale, causal,
-                  cur_stream());
+                  (int)dkv_variant, cur_stream());
   return {dQ, dK, dV};
 }
 
@@ -485,7 +490,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_step", &adamw_step);
   m.def("cross_entropy_fused", &cross_entropy_fused);
   m.def("attn_fwd", &attn_fwd);
-  m.def("attn_bwd", &attn_bwd);
+  m.def("attn_bwd", &attn_bwd, py::arg("Q"), py::arg("K"), py::arg("V"),
+        py::arg("O"), py::arg("dO"), py::arg("lse"), py::arg("scale"),
+        py::arg("causal"), py::arg("dkv_variant") = -1);
   m.def("attn_decode", &attn_decode);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8);
