@@ -155,6 +155,9 @@ class _RMSNormFn(torch.autograd.Function):
 
 
 def rmsnorm(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5):
+    """y = x * rsqrt(mean(x^2) + eps) * w over the last dim H.  On GPU H
+    must be a multiple of 8, and backward additionally needs H <= 16384
+    (one row's columns are held in registers); other widths raise."""
     return _RMSNormFn.apply(x, w, eps)
 
 
@@ -179,6 +182,12 @@ class _RoPEFn(torch.autograd.Function):
 
 
 def rope(x, cos, sin, positions):
+    """Rotary embedding of x [..., T, H, D] (D even) with fp32 tables
+    cos/sin [S, D/2]; positions [T] broadcasts over leading dims.  On GPU
+    positions must be int32 and the tables fp32 and contiguous (the
+    kernel raises otherwise)."""
+    if x.is_cuda and x.dim() > 3:  # the kernel reads one position per token
+        positions = positions.expand(x.shape[:-2]).reshape(-1)
     return _RoPEFn.apply(x, cos, sin, positions)
 
 
@@ -280,7 +289,7 @@ class _SwiGLUFn(torch.autograd.Function):
         (gu,) = ctx.saved_tensors
         if gu.is_cuda:
             C = native()
-            return C.swiglu_bwd(gu, dy.contiguous())
+            return C.swiglu_bwd(gu.contiguous(), dy.contiguous())
         M = gu.shape[-1] // 2
         g, u = gu.float().split(M, dim=-1)
         dyf = dy.float()
@@ -292,7 +301,8 @@ class _SwiGLUFn(torch.autograd.Function):
 
 
 def swiglu(gu):
-    """Fused silu(gate) * up over a fused [.., 2M] gate|up tensor."""
+    """Fused silu(gate) * up over a fused [.., 2M] gate|up tensor.  On
+    GPU M must be a multiple of 8 (16-byte vectors); other widths raise."""
     return _SwiGLUFn.apply(gu)
 
 

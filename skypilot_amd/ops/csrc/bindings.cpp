@@ -81,7 +81,12 @@ torch::Tensor rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
   CHECK_GPU(w); CHECK_CONTIG(w); CHECK_BF16(w);
   const int H = (int)x.size(-1);
   TORCH_CHECK(H % 8 == 0, "hidden dim must be a multiple of 8");
+  TORCH_CHECK(w.numel() == H, "rmsnorm_fwd: w must have H = ", H,
+              " elements, got ", w.numel());
   long long rows = x.numel() / H;
+  CHECK_GPU(inv_rms); CHECK_CONTIG(inv_rms);
+  TORCH_CHECK(inv_rms.scalar_type() == at::kFloat && inv_rms.numel() == rows,
+              "rmsnorm_fwd: inv_rms must be fp32 with one entry per row");
   auto y = torch::empty_like(x);
   rmsnorm_fwd_launch(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                      inv_rms.data_ptr<float>(), rows, H, (float)eps,
@@ -92,9 +97,22 @@ torch::Tensor rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor x, torch::Tensor w,
                                        torch::Tensor dy,
                                        torch::Tensor inv_rms) {
-  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_CONTIG(dy);
+  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  CHECK_GPU(w); CHECK_CONTIG(w); CHECK_BF16(w);
+  CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_BF16(dy);
+  CHECK_GPU(inv_rms); CHECK_CONTIG(inv_rms);
   const int H = (int)x.size(-1);
+  // The kernel keeps a row's columns in registers: 8 vectors of 8 per
+  // thread at block=256 is its widest instantiation.
+  TORCH_CHECK(H % 8 == 0 && H <= 16384,
+              "rmsnorm_bwd: hidden dim must be a multiple of 8 and at most "
+              "16384, got ", H);
+  TORCH_CHECK(w.numel() == H, "rmsnorm_bwd: w must have H = ", H,
+              " elements, got ", w.numel());
+  TORCH_CHECK(dy.sizes() == x.sizes(), "rmsnorm_bwd: dy must have x's shape");
   long long rows = x.numel() / H;
+  TORCH_CHECK(inv_rms.scalar_type() == at::kFloat && inv_rms.numel() == rows,
+              "rmsnorm_bwd: inv_rms must be fp32 with one entry per row");
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({(long)H},
                          x.options().dtype(at::kFloat));
@@ -109,10 +127,23 @@ torch::Tensor rope(torch::Tensor x, torch::Tensor cos_tab,
                    torch::Tensor sin_tab, torch::Tensor positions,
                    bool backward) {
   CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
-  TORCH_CHECK(positions.scalar_type() == at::kInt);
+  TORCH_CHECK(positions.scalar_type() == at::kInt,
+              "rope: positions must be int32");
+  CHECK_GPU(positions); CHECK_CONTIG(positions);
+  TORCH_CHECK(x.dim() >= 2, "rope: x must be [..., heads, head_dim]");
   const int D = (int)x.size(-1);
   const int H = (int)x.size(-2);
+  TORCH_CHECK(D % 2 == 0, "rope: head dim must be even, got ", D);
   long long n_tokens = x.numel() / ((long long)H * D);
+  TORCH_CHECK(positions.numel() == n_tokens, "rope: need one position per "
+              "token: ", n_tokens, " tokens, ", positions.numel(),
+              " positions");
+  for (const torch::Tensor& t : {cos_tab, sin_tab}) {
+    CHECK_GPU(t); CHECK_CONTIG(t);
+    TORCH_CHECK(t.scalar_type() == at::kFloat, "rope: cos/sin must be fp32");
+    TORCH_CHECK(t.dim() >= 1 && t.size(-1) == D / 2,
+                "rope: cos/sin last dim must be head_dim/2 = ", D / 2);
+  }
   auto y = torch::empty_like(x);
   rope_launch(x.data_ptr(), y.data_ptr(), cos_tab.data_ptr<float>(),
               sin_tab.data_ptr<float>(), positions.data_ptr<int>(), n_tokens,
@@ -431,6 +462,8 @@ torch::Tensor rope_kvwrite(torch::Tensor qkv, torch::Tensor kc,
 torch::Tensor swiglu_fwd(torch::Tensor gu) {
   CHECK_GPU(gu); CHECK_CONTIG(gu); CHECK_BF16(gu);
   const int M2 = (int)gu.size(-1);
+  TORCH_CHECK(M2 % 16 == 0, "swiglu_fwd: last dim must be 2*M with "
+              "M % 8 == 0, got ", M2);
   long long rows = gu.numel() / M2;
   auto sizes = gu.sizes().vec();
   sizes.back() = M2 / 2;
@@ -441,8 +474,15 @@ torch::Tensor swiglu_fwd(torch::Tensor gu) {
 }
 
 torch::Tensor swiglu_bwd(torch::Tensor gu, torch::Tensor dy) {
-  CHECK_GPU(gu); CHECK_CONTIG(dy);
+  CHECK_GPU(gu); CHECK_CONTIG(gu); CHECK_BF16(gu);
+  CHECK_GPU(dy); CHECK_CONTIG(dy); CHECK_BF16(dy);
   const int M2 = (int)gu.size(-1);
+  TORCH_CHECK(M2 % 16 == 0, "swiglu_bwd: last dim must be 2*M with "
+              "M % 8 == 0, got ", M2);
+  auto ysizes = gu.sizes().vec();
+  ysizes.back() = M2 / 2;
+  TORCH_CHECK(dy.sizes() == at::IntArrayRef(ysizes),
+              "swiglu_bwd: dy must have the shape of swiglu_fwd(gu)");
   long long rows = gu.numel() / M2;
   auto dgu = torch::empty_like(gu);
   swiglu_bwd_launch(gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(), rows,

@@ -50,8 +50,10 @@ extern "C" __global__ void rmsnorm_fwd_kernel(
 // Backward. Each block owns a fixed set of columns across all its rows so
 // per-thread dw partials stay in registers; one atomicAdd per column per
 // block at the end (device-scope atomics are correct cross-XCD, guide G12).
-// Assumes H <= 8 * 8 * blockDim.x (H<=16384 at block=256) so per-thread
-// dw registers fit; hidden sizes beyond that use the looped variant below.
+// Requires H % 8 == 0 and H <= 8 * NV * blockDim.x; the largest
+// instantiation is NV=8, so H <= 16384 at block=256 (per-thread dw registers
+// must fit).  There is no looped variant for wider rows: the binding
+// rejects them instead of leaving columns unwritten.
 template <int NV>
 __global__ void rmsnorm_bwd_kernel(
     const unsigned short* __restrict__ x, const unsigned short* __restrict__ w,

@@ -5,9 +5,10 @@
 // cos/sin [S, D/2] device buffers.
 //
 // Layout: x is [T, H, D] contiguous (T = B*S tokens), positions[T] gives
-// each token's table row.  Vectorized path (D % 32 == 0): 16 lanes per
-// (token, head) row, each lane rotates 4 pairs with 8B bf16 loads and
-// 16B table loads (guide §6 G13: scalar bf16 costs ~2-2.5x).
+// each token's table row.  Vectorized path (D % 128 == 0): 16 lanes per
+// (token, head) row, each lane rotates its D/32 pairs four at a time with
+// 8B bf16 loads and 16B table loads (guide §6 G13: scalar bf16 costs
+// ~2-2.5x).  Every other even D takes the scalar kernel.
 // backward == forward with -sin.
 #include "common.h"
 
@@ -16,6 +17,9 @@ extern "C" __global__ void rope_kernel_vec(
     const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
     const int* __restrict__ positions, long long n_tokens, int n_heads,
     int D, float sin_sign) {
+  // Requires D % 128 == 0: the p += 4 loop below moves 4 pairs per trip,
+  // so pairs_per_lane must be a multiple of 4 or a lane runs past its
+  // share of the row (and, in the last row, past the buffers).
   const int half = D / 2;
   const int lanes_per_row = 16;
   const int pairs_per_lane = half / lanes_per_row;  // 4 for D=128
@@ -54,7 +58,7 @@ extern "C" __global__ void rope_kernel_vec(
   }
 }
 
-// Scalar fallback for head dims not divisible by 32.
+// Scalar fallback for every even head dim that is not a multiple of 128.
 extern "C" __global__ void rope_kernel(
     const unsigned short* __restrict__ x, unsigned short* __restrict__ y,
     const float* __restrict__ cos_tab, const float* __restrict__ sin_tab,
@@ -88,7 +92,7 @@ extern "C" void rope_launch(const void* x, void* y, const float* cos_tab,
                             long long n_tokens, int n_heads, int D,
                             bool backward, hipStream_t stream) {
   const float ss = backward ? -1.f : 1.f;
-  if (D % 32 == 0) {
+  if (D % 128 == 0) {
     long long work = n_tokens * n_heads * 16;  // 16 lanes per row
     int grid = membound_grid(work, 256);
     hipLaunchKernelGGL(rope_kernel_vec, dim3(grid), dim3(256), 0, stream,
