@@ -1,7 +1,9 @@
-"""A/B timing: attention forward v3 (8-wave 32x32) vs round-1 swapped.
+"""Forward attention timer.
 
-Run twice with SKY_ATTN_FWD_V3=1/0 (the launcher caches the env at first
-dispatch).  Prints ms and TF/s at the flagship shape (causal FLOPs)."""
+Prints ms and TF/s (causal FLOPs) at B=AB_B (4), S=AB_S (4096), Hq32 Hkv8
+D128.  AB_S chooses the kernel: S % 256 == 0 runs the v3 forward, any
+other multiple of 64 the 64-tile forward.  SKY_BENCH_CAUSAL=0 times the
+non-causal case."""
 import os
 import sys
 import time
@@ -18,7 +20,7 @@ k = (torch.randn(B, S, Hkv, D, device=dev) * 0.5).bfloat16()
 v = (torch.randn(B, S, Hkv, D, device=dev) * 0.5).bfloat16()
 C = ops.native()
 
-label = os.environ.get("SKY_ATTN_FWD_V3", "1")
+label = "v3" if S % 256 == 0 else "64-tile"
 CAUSAL = os.environ.get("SKY_BENCH_CAUSAL", "1") == "1"
 O, lse = C.attn_fwd(q, k, v, D ** -0.5, CAUSAL)
 torch.cuda.synchronize()
@@ -30,5 +32,5 @@ torch.cuda.synchronize()
 ms = (time.perf_counter() - t0) / iters * 1e3
 # causal flops: 4 * B*Hq*D * S^2/2 (fwd = 2 matmuls)
 fl = 4.0 * B * Hq * D * S * S / (2 if CAUSAL else 1)
-print(f"[fwd v3={label} B={B} S={S} causal={CAUSAL}] {ms:.3f} ms  {fl / (ms * 1e-3) / 1e12:.0f} TF/s")
+print(f"[fwd {label} B={B} S={S} causal={CAUSAL}] {ms:.3f} ms  {fl / (ms * 1e-3) / 1e12:.0f} TF/s")
 sys.stdout.flush()

@@ -197,8 +197,10 @@ class _AttentionFn(torch.autograd.Function):
         ctx.scale, ctx.causal = scale, causal
         if q.is_cuda:
             C = _require_native("attention")
-            O, lse = C.attn_fwd(q.contiguous(), k.contiguous(),
-                                v.contiguous(), scale, causal)
+            # The kernels index dense [B,S,H,D]; backward gets the same
+            # dense tensors the forward ran on.
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+            O, lse = C.attn_fwd(q, k, v, scale, causal)
             ctx.save_for_backward(q, k, v, O, lse)
             ctx.native = True
             return O

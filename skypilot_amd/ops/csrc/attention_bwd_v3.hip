@@ -24,11 +24,8 @@
 // Math (identical to v1, attention_bwd.hip):
 //   P = exp(scale*QK^T - lse); dP = dO V^T; dS = P*(dP - Dvec);
 //   dV += P^T dO; dK += scale * dS^T Q; dQ = scale * dS K.
-#include <cstdlib>
-
+#include "attn_launch.h"
 #include "attn_v3.h"
-
-#define ATT_D 128
 
 // Q/dO tile layout for dkv: [32 q][128 d] in vsub subtiles with an
 // extra XOR on the d-chunk keyed by q>>2 — without it, b128 row-reads
@@ -818,9 +815,9 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dq_v3_kernel(
 }
 
 // dkv_variant: 0 = attn_bwd_dkv_v3_kernel, 1 = the pipelined kernel,
-// 2 = the pipelined kernel on the heavy-first grid; -1 = SKY_ATTN_DKV_PIPE
-// (same values) if set, else 2.  Measured per call at B6 S4096 Hq32 Hkv8
-// causal: 4.13 / 3.62 / 2.14 ms (docs/BENCHMARKS.md).
+// 2 = the pipelined kernel on the heavy-first grid; -1 = 2, the shipped
+// choice.  Measured per call at B6 S4096 Hq32 Hkv8 causal: 4.13 / 3.62 /
+// 2.14 ms (docs/BENCHMARKS.md).
 extern "C" void attn_bwd_v3_launch(const void* Q, const void* K,
                                    const void* V, const void* dO,
                                    const float* lse, const float* Dvec,
@@ -828,12 +825,7 @@ extern "C" void attn_bwd_v3_launch(const void* Q, const void* K,
                                    int S, int Hq, int Hkv, float scale,
                                    bool causal, int dkv_variant,
                                    hipStream_t stream) {
-  static const int dkv_env = [] {
-    const char* e = getenv("SKY_ATTN_DKV_PIPE");
-    const int v = e ? atoi(e) : 2;
-    return v < 0 || v > 2 ? 2 : v;
-  }();
-  const int variant = dkv_variant >= 0 ? dkv_variant : dkv_env;
+  const int variant = dkv_variant >= 0 ? dkv_variant : 2;
   if (variant == 0) {
     dim3 gkv(S / 128, B * Hkv);
     hipLaunchKernelGGL(attn_bwd_dkv_v3_kernel, gkv, dim3(256), 0, stream,

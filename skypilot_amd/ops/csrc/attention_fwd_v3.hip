@@ -1,9 +1,13 @@
-// Flash-attention forward v3 — 8-wave 32x32 swapped-operand schedule.
+// Flash-attention forward v3 — 4-wave 32x32 swapped-operand schedule.
 //
-// The round-2 deep-pipeline forward (guide §B "8-warp 32x32 ladder",
+// The round-2 deep-pipeline forward (guide §B "32x32 ladder",
 // techniques T2/T5/T10/T12/T13/T14 composed, not grafted):
-//   - 512-thread blocks: 8 waves, wave w owns q rows [32w, 32w+32) of a
-//     256-row q block; kv tiles of 64.
+//   - 256-thread blocks: 4 waves, wave w owns q rows [32w, 32w+32) of a
+//     128-row q block; kv tiles of 64.  Two such blocks share a CU and
+//     their phases interleave freely (round 1 measured that cross-block
+//     overlap beats one barrier-synced 512-thread block on these
+//     structures; the 8-wave form of this kernel measured 372 vs 394
+//     TF/s, docs/BENCHMARKS.md).
 //   - Swapped QK^T (S^T = K Q^T): each lane holds 32 kv-scores of ONE q
 //     column in MFMA C-registers, so the online softmax is 31 in-lane
 //     fmax + one lane<->lane+32 exchange — zero LDS softmax state.
@@ -23,30 +27,20 @@
 //
 // Layouts: Q,O [B,S,Hq,128]; K,V [B,S,Hkv,128]; lse [B,Hq,S] fp32
 // (natural-log convention, same as v1/v2 kernels).
-#include <cstdlib>
-#include "common.h"
-
-#define ATT_D 128
-#define KVB 64
-#define QBW 32
-#define NWV3 8
-#define QBLK3 (QBW * NWV3)  // 256 q rows per block (8-wave variant)
-
+#include "attn_launch.h"
 #include "attn_v3.h"
 
-// NW = waves per block (8 -> one 512-thread block/CU; 4 -> two
-// independent 256-thread blocks/CU whose phases interleave freely —
-// round-1 measured that cross-block overlap beats one barrier-synced
-// big block on these structures).
-template <int NW>
-__global__ __launch_bounds__(64 * NW, 2) void attn_fwd_v3_t(
+#define KVB 64  // kv rows per tile
+#define QBW 32  // q rows per wave
+#define NW 4    // waves per block
+
+extern "C" __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_v3_kernel(
     const unsigned short* __restrict__ Q, const unsigned short* __restrict__ K,
     const unsigned short* __restrict__ V, unsigned short* __restrict__ O,
     float* __restrict__ lse_out, int B, int S, int Hq, int Hkv, float scale,
     int causal) {
   constexpr int QB = QBW * NW;        // q rows per block
   constexpr int NKI = KVB / NW / 4;   // K global_load_lds per wave
-  constexpr int NVC = 16 / NW;        // V 16B chunks per thread
   __shared__ unsigned short k_lds[2][KVB * ATT_D];  // 2 x 16 KB
   __shared__ unsigned short v_lds[2][KVB * ATT_D];  // 2 x 16 KB
 
@@ -77,7 +71,6 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_v3_t(
 
   const long long q_rowstride = (long long)Hq * ATT_D;
   const long long kv_rowstride = (long long)Hkv * ATT_D;
-  const unsigned short* Qb = Q + ((long long)b * S * Hq + qh) * ATT_D;
   const unsigned short* Kb = K + ((long long)b * S * Hkv + kvh) * ATT_D;
   const unsigned short* Vb = V + ((long long)b * S * Hkv + kvh) * ATT_D;
 
@@ -108,16 +101,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_v3_t(
     for (int r = 0; r < 16; ++r) o_t[dn][r] = 0.f;
   float m_run = -INFINITY, l_run = 0.f;
 
-  // causal: 1 = normal; 2 = debug timing (causal loop structure, mask
-  // skipped); 3 = debug timing (no per-wave diagonal skip).
   const int nt_A = causal ? (qbase + QB) / KVB : S / KVB;
   const int nt_B = paired ? (qtB * QB + QB) / KVB : 0;
   const int total_t = nt_A + nt_B;
   // Tiles this wave actually computes (beyond its diagonal: staging +
   // barriers only).
-  int w_tiles = (causal == 1 || causal == 2)
-                    ? ((qbase + QBW * w + QBW - 1) >> 6) + 1
-                    : nt_A;
+  int w_tiles = causal ? ((qbase + QBW * w + QBW - 1) >> 6) + 1 : nt_A;
 
   // ---- epilogue: O[q][d] = O^T[d][q] / l; lse = ln2*m' + ln(l).
   unsigned short* Ob = O + ((long long)b * S * Hq + qh) * ATT_D;
@@ -173,8 +162,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_v3_t(
         for (int r = 0; r < 16; ++r) o_t[dn][r] = 0.f;
       m_run = -INFINITY;
       l_run = 0.f;
-      w_tiles = (causal == 3) ? nt_B
-                              : ((qbase + QBW * w + QBW - 1) >> 6) + 1;
+      w_tiles = ((qbase + QBW * w + QBW - 1) >> 6) + 1;
     }
     const int kt = it < nt_A ? it : it - nt_A;
     const int buf = it & 1;
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd_v3_t(
 
     // ---- causal mask (finite big-negative so exp2 underflows to 0;
     // m_run is already real for every row because tile 0 is unmasked).
-    if (causal == 1 && kvbase + KVB - 1 > qbase + QBW * w) {
+    if (causal && kvbase + KVB - 1 > qbase + QBW * w) {
 #pragma unroll
       for (int n = 0; n < 2; ++n)
 #pragma unroll
@@ -341,34 +329,12 @@ extern "C" void attn_fwd_v3_launch(const void* Q, const void* K,
                                    const void* V, void* O, float* lse, int B,
                                    int S, int Hq, int Hkv, float scale,
                                    bool causal, hipStream_t stream) {
-  static const int nw = [] {
-    const char* e = getenv("SKY_ATTN_FWD_V3_NW");
-    return e ? atoi(e) : 4;
-  }();
-  static const int dbg = [] {
-    const char* e = getenv("SKY_ATTN_DEBUG_MODE");
-    return e ? atoi(e) : 0;
-  }();
-  const int cz = causal ? (dbg ? dbg : 1) : 0;
-  static const int pair = [] {
-    const char* e = getenv("SKY_ATTN_FWD_V3_PAIR");
-    return e ? atoi(e) : 1;
-  }();
-  if (nw == 8) {
-    int nq = S / (QBW * 8);
-    int gx = (pair && cz && nq % 2 == 0) ? nq / 2 : nq;
-    dim3 grid(gx, B * Hq);
-    hipLaunchKernelGGL(attn_fwd_v3_t<8>, grid, dim3(512), 0, stream,
-                       (const unsigned short*)Q, (const unsigned short*)K,
-                       (const unsigned short*)V, (unsigned short*)O, lse, B,
-                       S, Hq, Hkv, scale, cz);
-    return;
-  }
-  int nq = S / (QBW * 4);
-  int gx = (pair && cz && nq % 2 == 0) ? nq / 2 : nq;
+  // Causal grids with an even q-tile count are paired (see the kernel).
+  int nq = S / (QBW * NW);
+  int gx = (causal && nq % 2 == 0) ? nq / 2 : nq;
   dim3 grid(gx, B * Hq);
-  hipLaunchKernelGGL(attn_fwd_v3_t<4>, grid, dim3(256), 0, stream,
+  hipLaunchKernelGGL(attn_fwd_v3_kernel, grid, dim3(64 * NW), 0, stream,
                      (const unsigned short*)Q, (const unsigned short*)K,
                      (const unsigned short*)V, (unsigned short*)O, lse, B, S,
-                     Hq, Hkv, scale, cz);
+                     Hq, Hkv, scale, causal ? 1 : 0);
 }

@@ -41,18 +41,6 @@ __device__ __forceinline__ float xhalf32(float x) {
   return (threadIdx.x & 32) ? r0.f : r1.f;
 }
 
-// Counted wait for a 2-deep tr-read pipeline: block until only the most
-// recent 8 lgkm ops (the next batch's tr reads) remain outstanding, and
-// bind the dependency to this batch's 8 destination registers.
-__device__ __forceinline__ void lgkm_wait8_bind2(tr4* a, tr4* b) {
-  asm volatile("s_waitcnt lgkmcnt(8)"
-               : "+v"(a->d[0]), "+v"(a->d[1]), "+v"(a->d[2]),
-                 "+v"(a->d[3]), "+v"(b->d[0]), "+v"(b->d[1]),
-                 "+v"(b->d[2]), "+v"(b->d[3])
-               :
-               : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
 // Drain outstanding global_load_lds before a buffer-handoff barrier.
 // LDS-DMA completion is tracked by VMcnt, and hipcc inserts only
 // `s_waitcnt lgkmcnt(0)` before s_barrier (verified in r02 ISA) — so
@@ -62,6 +50,8 @@ __device__ __forceinline__ void vm_drain() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// Wait for two ds_tr4_issue batches and bind the dependency to their 8
+// destination registers.
 __device__ __forceinline__ void lgkm_wait0_bind2(tr4* a, tr4* b) {
   asm volatile("s_waitcnt lgkmcnt(0)"
                : "+v"(a->d[0]), "+v"(a->d[1]), "+v"(a->d[2]),

@@ -10,6 +10,8 @@
 
 #include <vector>
 
+#include "attn_launch.h"
+
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
 #define CHECK_BF16(x) \
@@ -31,11 +33,6 @@ void adamw_launch(void*, float*, const void*, float*, float*, long long,
                   float, float, float, float, float, int, float, hipStream_t);
 void cross_entropy_launch(void*, const int*, float*, long long, int, float,
                           int, hipStream_t);
-void attn_fwd_launch(const void*, const void*, const void*, void*, float*,
-                     int, int, int, int, float, bool, hipStream_t);
-void attn_bwd_launch(const void*, const void*, const void*, const void*,
-                     const void*, const float*, float*, void*, void*, void*,
-                     int, int, int, int, float, bool, int, hipStream_t);
 void mfma_probe_launch(const void*, const void*, float*, hipStream_t);
 void mfma32_probe_launch(const void*, const void*, float*, hipStream_t);
 void trb16_probe_launch(float*, int, hipStream_t);
@@ -187,17 +184,43 @@ torch::Tensor cross_entropy_fused(torch::Tensor logits, torch::Tensor targets,
 }
 
 // ---- Attention ------------------------------------------------------------
+// The kernels index every tensor as dense [B,S,H,128] and tile S by 64:
+// anything else would read or write the wrong elements, so it is
+// rejected here.  `op` names the binding in the messages.
+static void check_attn_qkv(const char* op, const torch::Tensor& Q,
+                           const torch::Tensor& K, const torch::Tensor& V) {
+  const torch::Tensor* ts[] = {&Q, &K, &V};
+  const char* names[] = {"Q", "K", "V"};
+  for (int i = 0; i < 3; ++i) {
+    const torch::Tensor& t = *ts[i];
+    TORCH_CHECK(t.is_cuda(), op, ": ", names[i], " must be on GPU");
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", names[i],
+                " must be bf16, got ", t.scalar_type());
+    TORCH_CHECK(t.dim() == 4, op, ": ", names[i],
+                " must be [B, S, heads, 128], got ", t.dim(), " dims");
+    TORCH_CHECK(t.is_contiguous(), op, ": ", names[i],
+                " must be contiguous, got strides ", t.strides());
+    TORCH_CHECK(t.size(3) == ATT_D, op, ": ", names[i],
+                " head dim must be 128, got ", t.size(3));
+  }
+  const int64_t B = Q.size(0), S = Q.size(1), Hq = Q.size(2);
+  TORCH_CHECK(S % 64 == 0, op, ": seq len must be a multiple of 64, got ", S);
+  TORCH_CHECK(K.size(0) == B && K.size(1) == S, op,
+              ": K must be [B, S, Hkv, 128] with Q's B = ", B, " and S = ", S,
+              ", got ", K.sizes());
+  TORCH_CHECK(V.sizes() == K.sizes(), op, ": V must have K's shape ",
+              K.sizes(), ", got ", V.sizes());
+  const int64_t Hkv = K.size(2);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, op, ": Hq = ", Hq,
+              " must be a multiple of Hkv = ", Hkv);
+}
+
 std::vector<torch::Tensor> attn_fwd(torch::Tensor Q, torch::Tensor K,
                                     torch::Tensor V, double scale,
                                     bool causal) {
-  CHECK_GPU(Q); CHECK_CONTIG(Q); CHECK_CONTIG(K); CHECK_CONTIG(V);
-  CHECK_BF16(Q);
-  const int B = (int)Q.size(0), S = (int)Q.size(1), Hq = (int)Q.size(2),
-            D = (int)Q.size(3);
+  check_attn_qkv("attn_fwd", Q, K, V);
+  const int B = (int)Q.size(0), S = (int)Q.size(1), Hq = (int)Q.size(2);
   const int Hkv = (int)K.size(2);
-  TORCH_CHECK(D == 128, "attention kernel requires head_dim=128");
-  TORCH_CHECK(S % 64 == 0, "seq len must be a multiple of 64");
-  TORCH_CHECK(Hq % Hkv == 0);
   auto O = torch::empty_like(Q);
   auto lse = torch::empty({B, Hq, S}, Q.options().dtype(at::kFloat));
   attn_fwd_launch(Q.data_ptr(), K.data_ptr(), V.data_ptr(), O.data_ptr(),
@@ -211,13 +234,32 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor Q, torch::Tensor K,
                                     torch::Tensor dO, torch::Tensor lse,
                                     double scale, bool causal,
                                     int64_t dkv_variant) {
-  // dkv_variant: -1 = default (environment, else the shipped kernel);
-  // 0 = v3 dkv, 1 = pipelined v3 dkv, 2 = pipelined + heavy-first grid.
-  CHECK_GPU(Q); CHECK_CONTIG(dO);
+  // dkv_variant: -1 = default (the shipped kernel, 2); 0 = v3 dkv,
+  // 1 = pipelined v3 dkv, 2 = pipelined + heavy-first grid.
+  check_attn_qkv("attn_bwd", Q, K, V);
   TORCH_CHECK(dkv_variant >= -1 && dkv_variant <= 2,
               "attn_bwd: dkv_variant must be -1, 0, 1 or 2");
   const int B = (int)Q.size(0), S = (int)Q.size(1), Hq = (int)Q.size(2);
   const int Hkv = (int)K.size(2);
+  const torch::Tensor* outs[] = {&O, &dO};
+  const char* out_names[] = {"O", "dO"};
+  for (int i = 0; i < 2; ++i) {
+    const torch::Tensor& t = *outs[i];
+    TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16, "attn_bwd: ",
+                out_names[i], " must be bf16 on GPU, got ", t.scalar_type());
+    TORCH_CHECK(t.sizes() == Q.sizes(), "attn_bwd: ", out_names[i],
+                " must have Q's shape ", Q.sizes(), ", got ", t.sizes());
+    TORCH_CHECK(t.is_contiguous(), "attn_bwd: ", out_names[i],
+                " must be contiguous, got strides ", t.strides());
+  }
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat,
+              "attn_bwd: lse must be fp32 on GPU, got ", lse.scalar_type());
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq &&
+                  lse.size(2) == S,
+              "attn_bwd: lse must be [B, Hq, S] = [", B, ", ", Hq, ", ", S,
+              "], got ", lse.sizes());
+  TORCH_CHECK(lse.is_contiguous(),
+              "attn_bwd: lse must be contiguous, got strides ", lse.strides());
   auto dQ = torch::empty_like(Q);
   auto dK = torch::empty_like(K);
   auto dV = torch::empty_like(V);

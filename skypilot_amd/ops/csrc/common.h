@@ -57,16 +57,6 @@ __device__ __forceinline__ int swzT(int byte_off, int row) {
   return byte_off ^ (((row >> 3) & 7) << 4);
 }
 
-// Read-friendly transposed-tile swizzle: keyed on the LOW d bits so the
-// B/A-fragment reads (lanes sweep d = ct*16 + lrow, identical kv
-// offset) spread across banks (swzT keyed d>>3 leaves them ~4-way
-// conflicted — the dominant LDS stall measured in attention).  Writes
-// must then be the vectorized transpose-staging path (s16x4 at d-pairs
-// spanning ch and quad), which this keying also spreads.
-__device__ __forceinline__ int swzT2(int byte_off, int row) {
-  return byte_off ^ ((row & 7) << 4);
-}
-
 // Swizzle for the P / dS staging tiles ([q or kv rows][64] C-layout
 // scatter): writes vary the row as lgrp*4+r (only 2 distinct (row&7)
 // per instruction) but cols span 16 — keying on (row>>1) gives 4 row
@@ -76,39 +66,19 @@ __device__ __forceinline__ int swzP(int byte_off, int row) {
   return byte_off ^ (((row >> 1) & 7) << 4);
 }
 
-// Paired ds_read_b64_tr_b16: two transpose-reads + one waitcnt.
-// Semantics (HW-verified by trb16 probe, 2026-09-12): per 16-lane
-// group, out[lw][j] = in_lane[(lw>>2)+4j][lw&3] where in_lane[r] is the
-// 4 bf16 at lane r's address.  With per-lane addresses
+// ds_read_b64_tr_b16 semantics (HW-verified by trb16 probe, 2026-09-12):
+// per 16-lane group, out[lw][j] = in_lane[(lw>>2)+4j][lw&3] where
+// in_lane[r] is the 4 bf16 at lane r's address.  With per-lane addresses
 //   q(r) = qbase + (r>>2),  d(r) = dbase + (r&3)*4
-// over a row-major [seq][D] tile, the two reads assemble exactly the
-// MFMA B-fragment B[k=q][n=d] — no transposed staging copy needed.
-// The sched_barrier is required (guide rule #18): hipcc hoists
-// register-only MFMA past inline-asm lgkmcnt.
-__device__ __forceinline__ s16x8 ds_tr_b16_pair(unsigned int a0,
-                                                unsigned int a1) {
-  unsigned long long lo, hi;
-  asm volatile(
-      "ds_read_b64_tr_b16 %0, %2\n\t"
-      "ds_read_b64_tr_b16 %1, %3\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=v"(lo), "=v"(hi)
-      : "v"(a0), "v"(a1)
-      : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  union { unsigned long long u[2]; s16x8 v; } cvt;
-  cvt.u[0] = lo;
-  cvt.u[1] = hi;
-  return cvt.v;
-}
-
-// Split-phase tr reads for counted-wait pipelines (guide §5.5 T3):
-// ds_tr4_issue fires FOUR ds_read_b64_tr_b16 without waiting;
-// lgkm_wait4_bind blocks until only the most recent 4 lgkm ops remain
-// outstanding and binds the dependency to the destination registers so
-// the compiler cannot hoist consumers above the wait.  All LDS traffic
-// in the pipelined region must go through these helpers (a stray
-// compiler ds op breaks the count).
+// over a row-major [seq][D] tile, two reads assemble exactly the MFMA
+// B-fragment B[k=q][n=d] — no transposed staging copy needed.
+//
+// Split-phase tr reads (guide §5.5 T3): ds_tr4_issue fires FOUR
+// ds_read_b64_tr_b16 without waiting; the matching wait (attn_v3.h's
+// lgkm_wait0_bind2) binds the dependency to the destination registers so
+// the compiler cannot hoist consumers above it, and ends in a
+// sched_barrier (guide rule #18: hipcc hoists register-only MFMA past
+// inline-asm lgkmcnt).
 struct tr4 {
   unsigned long long d[4];
 };
@@ -123,38 +93,6 @@ __device__ __forceinline__ void ds_tr4_issue(tr4* t, unsigned a0,
       : "=v"(t->d[0]), "=v"(t->d[1]), "=v"(t->d[2]), "=v"(t->d[3])
       : "v"(a0), "v"(a1), "v"(a2), "v"(a3)
       : "memory");
-}
-__device__ __forceinline__ void lgkm_wait4_bind(tr4* t) {
-  asm volatile("s_waitcnt lgkmcnt(4)"
-               : "+v"(t->d[0]), "+v"(t->d[1]), "+v"(t->d[2]),
-                 "+v"(t->d[3])
-               :
-               : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-__device__ __forceinline__ void lgkm_wait0_bind(tr4* t) {
-  asm volatile("s_waitcnt lgkmcnt(0)"
-               : "+v"(t->d[0]), "+v"(t->d[1]), "+v"(t->d[2]),
-                 "+v"(t->d[3])
-               :
-               : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// Synchronous b128 LDS read through inline asm: used before a
-// counted-wait region so NO compiler-tracked ds op remains outstanding
-// (the compiler would otherwise insert its own s_waitcnt mid-region and
-// count our in-flight tr reads).
-__device__ __forceinline__ s16x8 ds_read_b128_sync(unsigned int addr) {
-  f32x4 d;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)"
-               : "=v"(d)
-               : "v"(addr)
-               : "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  union { f32x4 f; s16x8 s; } u;
-  u.f = d;
-  return u.s;
 }
 
 // bf16 <-> f32 via bit ops (we deliberately avoid __hip_bfloat16 so these

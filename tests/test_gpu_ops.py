@@ -317,8 +317,7 @@ def test_attention_shape_fuzz():
             (1, 64, 8, 8, True), (3, 128, 16, 2, True),
             (2, 256, 32, 8, False), (1, 1024, 8, 2, True),
             (2, 192, 4, 4, False),
-            # S % 256 == 0 routes to the v3 32x32 kernel (4-wave by
-            # default; SKY_ATTN_FWD_V3_NW=8 selects the 8-wave twin)
+            # S % 256 == 0 routes to the v3 32x32 kernel (4 waves)
             (2, 512, 16, 4, True), (1, 256, 8, 8, True),
             # v3 edge shapes around the r02 gl_lds barrier race:
             # minimal paired grid (nq=2), single-head, non-causal v3,
@@ -349,6 +348,69 @@ def test_attention_shape_fuzz():
                                    rtol=0.08, msg=str(cfg))
         torch.testing.assert_close(v.grad.float(), vf.grad, atol=0.08,
                                    rtol=0.08, msg=str(cfg))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,S,Hq,Hkv", [(1, 64, 2, 1),     # 64-tile fwd/bwd
+                                        (1, 256, 2, 2)])   # v3 fwd/bwd
+def test_attention_strided_inputs(B, S, Hq, Hkv):
+    """Non-contiguous q/k/v (transposed [B,H,S,D] views) through autograd:
+    the kernels index dense [B,S,H,D], so ops.attention must hand forward
+    AND backward the same dense copies.  Tolerances as in
+    test_attention_shape_fuzz."""
+    torch.manual_seed(11)
+
+    def strided(H):
+        t = (torch.randn(B, H, S, 128, device="cuda") * 0.5).bfloat16()
+        return t.transpose(1, 2).requires_grad_(True)
+
+    q, k, v = strided(Hq), strided(Hkv), strided(Hkv)
+    assert not q.is_contiguous()
+    out = ops.attention(q, k, v, 128 ** -0.5, causal=True)
+    g = torch.randn_like(out) * 0.5
+    out.backward(g)
+    qf = q.detach().float().requires_grad_(True)
+    kf = k.detach().float().requires_grad_(True)
+    vf = v.detach().float().requires_grad_(True)
+    ref = ops.attention_ref(qf, kf, vf, 128 ** -0.5, causal=True)
+    ref.backward(g.float())
+    torch.testing.assert_close(out.float(), ref, atol=0.05, rtol=0.05)
+    torch.testing.assert_close(q.grad.float(), qf.grad, atol=0.08, rtol=0.08)
+    torch.testing.assert_close(k.grad.float(), kf.grad, atol=0.08, rtol=0.08)
+    torch.testing.assert_close(v.grad.float(), vf.grad, atol=0.08, rtol=0.08)
+
+
+@pytest.mark.gpu
+def test_attention_bindings_reject_bad_inputs():
+    """attn_fwd / attn_bwd raise before any launch on what the kernels
+    cannot index; everything else in each call is valid at
+    (B, S, Hq, Hkv) = (1, 64, 2, 1)."""
+    C = ops.native()
+    B, S, Hq, Hkv, D = 1, 64, 2, 1, 128
+    scale = D ** -0.5
+
+    def bf(*shape):
+        return (torch.randn(*shape, device="cuda") * 0.5).bfloat16()
+
+    q, k, v = bf(B, S, Hq, D), bf(B, S, Hkv, D), bf(B, S, Hkv, D)
+    O, lse = C.attn_fwd(q, k, v, scale, True)
+    dO = bf(B, S, Hq, D)
+
+    q_strided = bf(B, Hq, S, D).transpose(1, 2)
+    assert not q_strided.is_contiguous()
+    with pytest.raises(RuntimeError, match="Q must be contiguous"):
+        C.attn_bwd(q_strided, k, v, O, dO, lse, scale, True)
+    with pytest.raises(RuntimeError, match="lse must be"):
+        C.attn_bwd(q, k, v, O, dO, lse.transpose(1, 2).contiguous(), scale,
+                   True)
+    with pytest.raises(RuntimeError, match="K head dim must be 128"):
+        C.attn_bwd(q, bf(B, S, Hkv, 64), v, O, dO, lse, scale, True)
+    with pytest.raises(RuntimeError, match="multiple of 64"):
+        C.attn_fwd(bf(B, 96, Hq, D), bf(B, 96, Hkv, D), bf(B, 96, Hkv, D),
+                   scale, True)
+    with pytest.raises(RuntimeError, match="K must be bf16"):
+        C.attn_fwd(q, k.half(), v, scale, True)
+    torch.cuda.synchronize()
 
 
 @pytest.mark.gpu
