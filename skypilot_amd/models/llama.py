@@ -82,6 +82,24 @@ def rope_tables(cfg: LlamaConfig, device, dtype=torch.float32):
     return freqs.cos().to(dtype).contiguous(), freqs.sin().to(dtype).contiguous()
 
 
+def append_attention(attn, q, k, v, infer_ctx):
+    """Chunked prefill (infer_ctx.mode == "append"): row i of sequence b
+    is the token at position append_start[b] + i.  The chunk's valid K/V
+    rows go into the cache first; attention then reads K/V from the cache
+    only, so the chunk sees the rows earlier chunks left there.  Shared
+    by Attention and the tensor-parallel TPAttention."""
+    cache = infer_ctx.cache
+    for i, (slot, start, ln) in enumerate(zip(infer_ctx.append_slots_l,
+                                              infer_ctx.append_start_l,
+                                              infer_ctx.append_lens_l)):
+        cache.write_append(attn.layer_idx, slot, start, k[i:i + 1],
+                           v[i:i + 1], ln)
+    return ops.attn_append(q, cache.k[attn.layer_idx],
+                           cache.v[attn.layer_idx], infer_ctx.append_slots,
+                           infer_ctx.append_start, infer_ctx.append_lens,
+                           attn.scale)
+
+
 class Attention(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
@@ -148,6 +166,8 @@ class Attention(nn.Module):
                      positions).view(B, S, self.n_kv, d)
         if infer_ctx is None:
             o = ops.attention(q, k, v, self.scale, causal=True)
+        elif infer_ctx.mode == "append":
+            o = append_attention(self, q, k, v, infer_ctx)
         else:  # prefill: plain causal attention over the prompt; the
             # (unpadded) K/V rows land in the cache for decode.  Rows of
             # a batched prefill are independent sequences.
@@ -265,6 +285,11 @@ class Llama(nn.Module):
             return logits
         for blk in self.blocks:
             x = blk(x, cos, sin, positions, infer_ctx)
+        if infer_ctx is not None and infer_ctx.mode == "append":
+            # Only the last valid row of each chunk can be sampled from:
+            # gather it before the norm and the vocab-sized GEMM.  -> [n,1,V]
+            last = (infer_ctx.append_lens.long() - 1).clamp(min=0)
+            x = x[torch.arange(B, device=x.device), last].unsqueeze(1)
         x = ops.rmsnorm(x, self.final_norm, self.cfg.norm_eps)
         return self.lm_head(x)
 

@@ -28,6 +28,7 @@ HIP_SOURCES = [
     "attention_bwd.hip",
     "attention_bwd_v3.hip",
     "attention_decode.hip",
+    "attention_append.hip",
     "swiglu.hip",
     "skinny_gemm.hip",
     "wgrad_gemm.hip",

@@ -10,6 +10,7 @@
 
 #include <vector>
 
+#include "attn_append.h"
 #include "attn_launch.h"
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
@@ -286,6 +287,66 @@ torch::Tensor attn_decode(torch::Tensor Q, torch::Tensor Kc,
                      O.data_ptr(), kv_lens.data_ptr<int>(),
                      slot_ids.data_ptr<int>(), B, S_max, Hq,
                      Hkv, (float)scale, cur_stream());
+  return O;
+}
+
+// Append attention over the slot KV cache (attention_append.hip): Sq new
+// rows per sequence against cache rows [0, q_start + q_len).  The kernel
+// indexes Q as dense [n,Sq,Hq,128] and the caches as dense
+// [slots,S_max,Hkv,128]; the index tensors stay on the device.
+torch::Tensor attn_append(torch::Tensor Q, torch::Tensor Kc,
+                          torch::Tensor Vc, torch::Tensor slot_ids,
+                          torch::Tensor q_start, torch::Tensor q_lens,
+                          double scale) {
+  const char* op = "attn_append";
+  const torch::Tensor* ts[] = {&Q, &Kc, &Vc};
+  const char* names[] = {"Q", "Kc", "Vc"};
+  for (int i = 0; i < 3; ++i) {
+    const torch::Tensor& t = *ts[i];
+    TORCH_CHECK(t.is_cuda(), op, ": ", names[i], " must be on GPU");
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16, op, ": ", names[i],
+                " must be bf16, got ", t.scalar_type());
+    TORCH_CHECK(t.dim() == 4, op, ": ", names[i],
+                " must have 4 dims [.., .., heads, 128], got ", t.dim());
+    TORCH_CHECK(t.is_contiguous(), op, ": ", names[i],
+                " must be contiguous, got strides ", t.strides());
+    TORCH_CHECK(t.size(3) == ATT_D, op, ": ", names[i],
+                " head dim must be 128, got ", t.size(3));
+  }
+  const int64_t n = Q.size(0), Sq = Q.size(1), Hq = Q.size(2);
+  const int64_t slots = Kc.size(0), S_max = Kc.size(1), Hkv = Kc.size(2);
+  TORCH_CHECK(Sq > 0 && Sq % 64 == 0, op,
+              ": chunk length Sq must be a positive multiple of 64, got ",
+              Sq);
+  TORCH_CHECK(Vc.sizes() == Kc.sizes(), op, ": Vc must have Kc's shape ",
+              Kc.sizes(), ", got ", Vc.sizes());
+  TORCH_CHECK(slots > 0 && S_max > 0, op,
+              ": the cache must hold at least one slot and one row, got ",
+              Kc.sizes());
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, op, ": Hq = ", Hq,
+              " must be a multiple of Hkv = ", Hkv);
+  TORCH_CHECK(n > 0 && n * Hq <= 65535, op, ": n * Hq = ", n * Hq,
+              " must be in [1, 65535] (one grid row per sequence and head)");
+  TORCH_CHECK(Q.device() == Kc.device() && Q.device() == Vc.device(), op,
+              ": Q, Kc and Vc must be on one device");
+  const torch::Tensor* idx[] = {&slot_ids, &q_start, &q_lens};
+  const char* idx_names[] = {"slot_ids", "q_start", "q_lens"};
+  for (int i = 0; i < 3; ++i) {
+    const torch::Tensor& t = *idx[i];
+    TORCH_CHECK(t.is_cuda() && t.device() == Q.device(), op, ": ",
+                idx_names[i], " must be on Q's GPU");
+    TORCH_CHECK(t.scalar_type() == at::kInt, op, ": ", idx_names[i],
+                " must be int32, got ", t.scalar_type());
+    TORCH_CHECK(t.dim() == 1 && t.size(0) == n && t.is_contiguous(), op,
+                ": ", idx_names[i], " must be a contiguous [n] = [", n,
+                "] tensor, got ", t.sizes());
+  }
+  auto O = torch::empty_like(Q);
+  attn_append_launch(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
+                     O.data_ptr(), slot_ids.data_ptr<int>(),
+                     q_start.data_ptr<int>(), q_lens.data_ptr<int>(), (int)n,
+                     (int)Sq, (int)Hq, (int)Hkv, (int)slots, (int)S_max,
+                     (float)scale, cur_stream());
   return O;
 }
 
@@ -576,6 +637,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("O"), py::arg("dO"), py::arg("lse"), py::arg("scale"),
         py::arg("causal"), py::arg("dkv_variant") = -1);
   m.def("attn_decode", &attn_decode);
+  m.def("attn_append", &attn_append);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8);
   m.def("transpose_bf16", &transpose_bf16);

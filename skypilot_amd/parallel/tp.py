@@ -109,6 +109,8 @@ class TPAttention(nn.Module):
                 infer_ctx.cache.write_prefill(self.layer_idx, slot,
                                               k[i:i + 1], v[i:i + 1], ln)
             o = ops.attention(q, k, v, self.scale, causal=True)
+        elif infer_ctx.mode == "append":
+            o = L.append_attention(self, q, k, v, infer_ctx)
         else:
             infer_ctx.cache.write_decode(self.layer_idx, infer_ctx.slots,
                                          infer_ctx.pos, k, v)

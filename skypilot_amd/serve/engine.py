@@ -6,6 +6,11 @@ SURVEY.md §2.11).  Prefill runs the causal flash kernel (prompt padded
 to the 64-row tile); decode steps batch every active sequence into one
 forward through the decode-attention kernel.  max_batch is sized to the
 288 GB HBM budget (KVCache.sized_for_memory).
+
+With ``prefill_chunk`` set, prompts are prefilled in chunks of that many
+tokens through the append-attention kernel (ops.attn_append), one chunk
+forward per loop iteration between decode steps, so a running stream
+waits for one chunk and never for a whole prompt.
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ from skypilot_amd.serve.kv_cache import KVCache
 @dataclass
 class InferenceContext:
     cache: KVCache
-    mode: str  # "prefill" | "decode"
+    mode: str  # "prefill" | "decode" | "append"
     prefill_slot: int = -1
     prefill_len: int = 0
     # batched prefill: one row per new sequence (all rows share
@@ -40,6 +45,16 @@ class InferenceContext:
     pos: Optional[torch.Tensor] = None          # int64 [n] write positions
     kv_lens: Optional[torch.Tensor] = None      # int32 [n] incl. new token
     slot_ids_i32: Optional[torch.Tensor] = None  # int32 [n]
+    # append (chunked prefill): row i of sequence b is the token at
+    # position append_start[b] + i; rows >= append_lens[b] are padding.
+    # int32 [n] device tensors for the kernel, host lists for the cache
+    # writes.
+    append_slots: Optional[torch.Tensor] = None
+    append_start: Optional[torch.Tensor] = None
+    append_lens: Optional[torch.Tensor] = None
+    append_slots_l: Optional[list] = None
+    append_start_l: Optional[list] = None
+    append_lens_l: Optional[list] = None
 
 
 @dataclass
@@ -58,12 +73,32 @@ class Request:
     finished_at: Optional[float] = None
 
 
+@dataclass
+class _Prefilling:
+    """A request whose prompt is being prefilled chunk by chunk."""
+    req: Request
+    slot: int
+    done: int = 0  # prompt tokens already in the cache
+
+
 class Engine:
     def __init__(self, model_name: str, device: Optional[str] = None,
                  max_seq: int = 4096, max_batch: Optional[int] = None,
                  hbm_budget_gb: Optional[float] = None,
                  use_graphs: bool = True, model=None, tp_group=None,
-                 tp_rank: int = 0, tp_world: int = 1):
+                 tp_rank: int = 0, tp_world: int = 1,
+                 prefill_chunk: Optional[int] = None):
+        # Chunked prefill: None keeps whole-prompt prefills (_prefill).
+        # The append kernel tiles the chunk by 64 rows.
+        if prefill_chunk is not None and (
+                isinstance(prefill_chunk, bool)
+                or not isinstance(prefill_chunk, int)
+                or prefill_chunk <= 0 or prefill_chunk % 64 != 0):
+            raise ValueError(
+                "prefill_chunk must be None or a positive multiple of 64, "
+                f"got {prefill_chunk!r}")
+        self.prefill_chunk = prefill_chunk
+        self.prefilling: List[_Prefilling] = []
         self.device = torch.device(device or (
             "cuda" if torch.cuda.is_available() else "cpu"))
         dtype = torch.bfloat16
@@ -221,6 +256,67 @@ class Engine:
             self.stats["prefill_tokens"] += lens[i]
             self._maybe_finish(slot, req, next_id)
 
+    # -------------------------- chunked prefill ------------------------
+    @torch.no_grad()
+    def _append_forward(self, slots, starts, lens, chunks) -> torch.Tensor:
+        """One append forward: sequence i adds tokens chunks[i] (lens[i]
+        of them) at positions starts[i].. to cache slot slots[i].
+        Returns the logits of each sequence's last valid row, [n, 1, V].
+        The leader and the TP followers run exactly this."""
+        n = len(slots)
+        sq = max(64, (max(lens) + 63) // 64 * 64)
+        toks = torch.zeros(n, sq, dtype=torch.long, device=self.device)
+        for i, ids in enumerate(chunks):
+            toks[i, :lens[i]] = torch.tensor(ids, dtype=torch.long,
+                                             device=self.device)
+
+        def i32(vals):
+            return torch.tensor(vals, dtype=torch.int32, device=self.device)
+
+        start_t = i32(starts)
+        # padding rows stay inside the rope tables
+        positions = (start_t[:, None] + torch.arange(
+            sq, dtype=torch.int32, device=self.device)[None, :]).clamp_(
+                max=self.cfg.max_seq_len - 1).reshape(-1)
+        ctx = InferenceContext(
+            cache=self.cache, mode="append", append_slots=i32(slots),
+            append_start=start_t, append_lens=i32(lens),
+            append_slots_l=list(slots), append_start_l=list(starts),
+            append_lens_l=list(lens))
+        return self.model(toks, positions, ctx)
+
+    @torch.no_grad()
+    def _append_step(self) -> None:
+        """Advance up to 16 prefilling requests by one chunk each, in one
+        forward; requests whose prompt is now complete sample their first
+        token and join the decode set."""
+        batch = self.prefilling[:16]
+        slots = [e.slot for e in batch]
+        starts = [e.done for e in batch]
+        lens = [min(self.prefill_chunk, len(e.req.prompt_ids) - e.done)
+                for e in batch]
+        chunks = [e.req.prompt_ids[s:s + l]
+                  for e, s, l in zip(batch, starts, lens)]
+        self._tp_bcast({"op": "append", "slots": slots, "starts": starts,
+                        "lens": lens, "chunks": chunks})
+        logits = self._append_forward(slots, starts, lens, chunks)
+        for i, e in enumerate(batch):
+            e.done += lens[i]
+            self.stats["prefill_tokens"] += lens[i]
+            if e.done < len(e.req.prompt_ids):
+                continue
+            req, slot = e.req, e.slot
+            next_id = self._sample(logits[i, 0], req.temperature, req.top_p)
+            self.cache.lens[slot] = e.done
+            req.out_ids.append(next_id)
+            if req.stream_queue is not None:
+                req.stream_queue.put(next_id)
+            req.first_token_at = time.time()
+            self.active[slot] = req
+            self._maybe_finish(slot, req, next_id)
+        self.prefilling = [e for e in self.prefilling
+                           if e.done < len(e.req.prompt_ids)]
+
     # -------------------------- hipGraph decode ------------------------
     # Max chained graph replays between host syncs (SKY_DECODE_CHUNK to
     # tune; measured flat 8..32 at 1 stream, so 8 keeps token-streaming
@@ -301,7 +397,8 @@ class Engine:
             b = self._bucket(n)
             all_greedy = all(r.temperature == 0 for r in reqs)
             chunk = 1
-            if all_greedy and self.pending.empty():
+            if (all_greedy and self.pending.empty()
+                    and not self.prefilling):
                 rem = min(r.max_tokens - len(r.out_ids) for r in reqs)
                 cap = min(self.max_seq - 2 - l for l in lens)
                 chunk = max(1, min(self.CHUNK, rem, cap))
@@ -436,6 +533,8 @@ class Engine:
                 return
             if msg["op"] == "prefill":
                 self._follow_prefill(msg)
+            elif msg["op"] == "append":
+                self._follow_append(msg)
             else:
                 self._follow_decode(msg)
 
@@ -452,6 +551,11 @@ class Engine:
         ctx = InferenceContext(cache=self.cache, mode="prefill",
                                prefill_slots=slots, prefill_lens=lens)
         self.model(toks, positions, ctx)
+
+    @torch.no_grad()
+    def _follow_append(self, msg) -> None:
+        self._append_forward(msg["slots"], msg["starts"], msg["lens"],
+                             msg["chunks"])
 
     @torch.no_grad()
     def _follow_decode(self, msg) -> None:
@@ -505,6 +609,25 @@ class Engine:
     def _loop_inner(self):
         while not self._stop.is_set():
             did = False
+            if self.prefill_chunk is not None:
+                # Chunked prefill: admission only takes a slot; each
+                # iteration runs one chunk forward, then one decode step.
+                while self.free_slots and not self.pending.empty():
+                    try:
+                        req = self.pending.get_nowait()
+                    except queue.Empty:
+                        break
+                    self.prefilling.append(
+                        _Prefilling(req, self.free_slots.pop()))
+                if self.prefilling:
+                    self._append_step()
+                    did = True
+                if self.active:
+                    self._decode_step()
+                    did = True
+                if not did:
+                    time.sleep(0.005)
+                continue
             # Admit pending requests while slots are free — batched
             # (up to 16 per prefill forward).
             batch: List[Request] = []

@@ -166,6 +166,11 @@ def main():
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--max-seq", type=int, default=4096)
     ap.add_argument("--max-batch", type=int, default=None)
+    ap.add_argument("--prefill-chunk", type=int, default=None,
+                    help="prefill prompts in chunks of this many tokens "
+                         "(a multiple of 64) between decode steps, so a "
+                         "long prompt does not stall running streams; "
+                         "default: whole-prompt prefill")
     ap.add_argument("--device", default=None)
     ap.add_argument("--fp8-decode", action="store_true",
                     help="quantize weights to rowwise e4m3fn for the "
@@ -195,7 +200,8 @@ def main():
                                device=device)
         engine = Engine(args.model, device=device, max_seq=args.max_seq,
                         max_batch=args.max_batch, model=shard,
-                        tp_rank=rank, tp_world=args.tp)
+                        tp_rank=rank, tp_world=args.tp,
+                        prefill_chunk=args.prefill_chunk)
         if args.fp8_decode:
             engine.enable_fp8_decode()
         if rank > 0:
@@ -210,7 +216,8 @@ def main():
                     log_level="warning")
         return
     engine = Engine(args.model, device=args.device, max_seq=args.max_seq,
-                    max_batch=args.max_batch)
+                    max_batch=args.max_batch,
+                    prefill_chunk=args.prefill_chunk)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode()
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)

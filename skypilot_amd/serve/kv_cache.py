@@ -48,6 +48,13 @@ class KVCache:
         self.k[layer][slot, :length] = k[0, :length]
         self.v[layer][slot, :length] = v[0, :length]
 
+    def write_append(self, layer: int, slot: int, start: int,
+                     k: torch.Tensor, v: torch.Tensor, length: int) -> None:
+        """k/v: [1, Sq_padded, Hkv, D], one chunk of a longer prompt;
+        store its first `length` rows at [slot, start:start+length]."""
+        self.k[layer][slot, start:start + length] = k[0, :length]
+        self.v[layer][slot, start:start + length] = v[0, :length]
+
     def write_decode(self, layer: int, slots: torch.Tensor,
                      pos: torch.Tensor, k: torch.Tensor,
                      v: torch.Tensor) -> None:
