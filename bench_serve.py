@@ -67,17 +67,28 @@ def main():
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked prefill: tokens per append forward "
                          "(multiple of 64); default whole-prompt prefill")
+    ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=None,
+                    help="request i of a batch uses seed + i")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="sample in the decode graph instead of on the host")
     ap.add_argument("--stall-prompts", type=int, default=0,
                     help="after the batches, also measure what a running "
                          "stream sees when this many --prompt-len prompts "
                          "arrive mid-decode (largest inter-token gap)")
     args = ap.parse_args()
+    if ((args.top_k > 0 or args.seed is not None)
+            and not args.device_sampling):
+        ap.error("--top-k and --seed need --device-sampling")
 
     from skypilot_amd.serve.engine import Engine
     eng = Engine(args.model,
                  device="cuda:0" if torch.cuda.is_available() else "cpu",
                  max_seq=4096, max_batch=args.max_batch,
-                 prefill_chunk=args.prefill_chunk)
+                 prefill_chunk=args.prefill_chunk,
+                 device_sampling=args.device_sampling)
     if args.fp8:
         print(f"fp8 decode weights: {eng.enable_fp8_decode()} tensors")
     eng.start()
@@ -91,15 +102,19 @@ def main():
         ttfts = []
         t0 = time.perf_counter()
 
-        def worker():
-            req = eng.submit(Request(prompt_ids=list(prompt),
-                                     max_tokens=args.gen_len))
+        def worker(i):
+            req = eng.submit(Request(
+                prompt_ids=list(prompt), max_tokens=args.gen_len,
+                temperature=args.temperature, top_p=args.top_p,
+                top_k=args.top_k,
+                seed=None if args.seed is None else args.seed + i))
             req.done.wait(1200)
             results.append(len(req.out_ids))
             if req.first_token_at:
                 ttfts.append(req.first_token_at - req.created)
 
-        threads = [threading.Thread(target=worker) for _ in range(nb)]
+        threads = [threading.Thread(target=worker, args=(i,))
+                   for i in range(nb)]
         for t in threads:
             t.start()
         for t in threads:
@@ -112,7 +127,9 @@ def main():
         print(f"concurrency {nb:3d}: {toks} tokens in {dt:6.2f}s = "
               f"{toks/dt:8.1f} tok/s decode | ttft p50 {p50:6.1f} ms "
               f"p95 {p95:6.1f} ms (prompt {args.prompt_len}, "
-              f"prefill_chunk {args.prefill_chunk})",
+              f"prefill_chunk {args.prefill_chunk}, temperature "
+              f"{args.temperature}, top_p {args.top_p}, top_k "
+              f"{args.top_k}, device_sampling {args.device_sampling})",
               flush=True)
     if args.stall_prompts:
         stall_probe(eng, prompt, args)

@@ -510,6 +510,176 @@ def decode_advance(logits, stage, ring, ctr):
     C.decode_advance(logits.contiguous(), stage, ring, ctr)
 
 
+# ---- seeded decode sampling (docs/KERNELS.md "Decode sampling") -----------
+_M32 = 0xFFFFFFFF
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10: 4 counter words and 2 key words in, 4 words out."""
+    c0, c1, c2, c3 = (int(x) & _M32 for x in counter)
+    k0, k1 = (int(x) & _M32 for x in key)
+    for r in range(10):
+        if r:
+            k0 = (k0 + 0x9E3779B9) & _M32
+            k1 = (k1 + 0xBB67AE85) & _M32
+        p0 = 0xD2511F53 * c0
+        p1 = 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0, p1 & _M32,
+                          (p0 >> 32) ^ c3 ^ k1, p0 & _M32)
+    return (c0, c1, c2, c3)
+
+
+def sample_uniform(seed: int, counter: int) -> float:
+    """u in [0, 1) for one draw: the top 24 bits of Philox word 0."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    x = philox4x32_10((int(counter) & _M32, 0, 0, 0),
+                      (seed & _M32, seed >> 32))[0]
+    return (x >> 8) * 2.0 ** -24
+
+
+def sample_row_reference(row, temperature, top_p, top_k, seed, counter):
+    """One row of the sampling definition in fp64.  Returns a dict with
+    the token and tau, and for sampled rows also the kept mask, the
+    index-order prefix sums C over the kept set, Z_K and t = u * Z_K
+    (what the GPU tests need to judge a kernel's token)."""
+    l = row.detach().to("cpu").float().double().reshape(-1)
+    V = l.numel()
+    T, p, k = float(temperature), float(top_p), int(top_k)
+    nan = torch.isnan(l)
+    greedy_src = torch.where(nan, torch.full_like(l, float("-inf")), l)
+    amax = int(greedy_src.argmax())      # first maximum; 0 if all -inf/NaN
+    m = float(greedy_src[amax])
+    out = {"token": amax, "tau": float("-inf"), "kept": None}
+    if not T > 0 or bool(nan.any()) or not math.isfinite(m):
+        return out
+    w = torch.exp((l - m) / T)
+    w[l == float("-inf")] = 0.0
+    Z = float(w.sum())
+    tau = float("-inf")
+    if 0 < k < V:
+        tau = max(tau, float(torch.sort(l, descending=True).values[k - 1]))
+    if p < 1.0:
+        if p <= 0.0:
+            tau = max(tau, m)
+        else:
+            vals, inv = torch.unique(l, return_inverse=True)  # ascending
+            gm = torch.zeros_like(vals).index_add_(0, inv, w)
+            above = gm.flip(0).cumsum(0)   # mass at or above, descending
+            hit = (above >= p * Z).nonzero()
+            i = int(hit[0]) if hit.numel() else vals.numel() - 1
+            tau = max(tau, float(vals.flip(0)[i]))
+    kept = l >= tau
+    C = torch.where(kept, w, torch.zeros_like(w)).cumsum(0)
+    ZK = float(C[-1])
+    t = sample_uniform(seed, counter) * ZK
+    hit = (kept & (C > t)).nonzero()
+    tok = int(hit[0]) if hit.numel() else int(kept.nonzero()[-1])
+    out.update(token=tok, tau=tau, kept=kept, C=C, ZK=ZK, t=t)
+    return out
+
+
+def pack_samp(n, temperature, top_p, top_k, seed, counter=0):
+    """CPU int32 [6, n]: temperature bits, top_p bits, top_k, seed_lo,
+    seed_hi, counter.  Rows 0..4 are the `samp` block that
+    decode_sample_advance takes, row 5 the counters of sample_tokens.
+    Each argument is a scalar or n per-row values; top_k is clamped to
+    int32 (any value outside [1, V) turns the filter off)."""
+    def rowvec(x, dtype):
+        if isinstance(x, torch.Tensor):
+            t = x.detach().to(device="cpu").to(dtype).reshape(-1)
+        else:
+            t = torch.tensor(x, dtype=dtype).reshape(-1)
+        return t.expand(n) if t.numel() == 1 else t
+
+    def wrap64(x):
+        if isinstance(x, torch.Tensor):
+            return x
+        if isinstance(x, (list, tuple)):
+            return [wrap64(v) for v in x]
+        x = int(x) & 0xFFFFFFFFFFFFFFFF
+        return x - (1 << 64) if x >= (1 << 63) else x
+
+    def wrap32(x):
+        if isinstance(x, torch.Tensor):
+            return x
+        if isinstance(x, (list, tuple)):
+            return [wrap32(v) for v in x]
+        x = int(x) & _M32
+        return x - (1 << 32) if x >= (1 << 31) else x
+
+    def clamp_k(x):
+        if isinstance(x, torch.Tensor):
+            return x
+        if isinstance(x, (list, tuple)):
+            return [clamp_k(v) for v in x]
+        return max(0, min(int(x), 2 ** 31 - 1))
+
+    sd = rowvec(wrap64(seed), torch.int64)
+    blk = torch.empty(6, n, dtype=torch.int32)
+    blk[0] = rowvec(temperature, torch.float32).contiguous().view(torch.int32)
+    blk[1] = rowvec(top_p, torch.float32).contiguous().view(torch.int32)
+    blk[2] = rowvec(clamp_k(top_k), torch.int64).clamp(
+        0, 2 ** 31 - 1).to(torch.int32)
+    blk[3] = (sd & _M32).to(torch.int32)      # wraps to the low 32 bits
+    blk[4] = (sd >> 32).to(torch.int32)
+    blk[5] = rowvec(wrap32(counter), torch.int64).to(torch.int32)
+    return blk
+
+
+def sample_tokens_reference(logits, temperature, top_p, top_k, seed,
+                            counter):
+    """fp64 CPU reference of the decode sampling definition: logits
+    [n, V] and per-row (or scalar) parameters -> (tokens int64 [n],
+    tau fp32 [n]).  temperature and top_p are taken at fp32 precision,
+    as the kernel receives them."""
+    logits = logits.reshape(-1, logits.shape[-1])
+    n = logits.shape[0]
+    blk = pack_samp(n, temperature, top_p, top_k, seed, counter)
+    Ts = blk[0].view(torch.float32).tolist()
+    ps = blk[1].view(torch.float32).tolist()
+    ks = blk[2].tolist()
+    los, his, cs = blk[3].tolist(), blk[4].tolist(), blk[5].tolist()
+    toks, taus = [], []
+    for i in range(n):
+        sd = ((his[i] & _M32) << 32) | (los[i] & _M32)
+        r = sample_row_reference(logits[i], Ts[i], ps[i], ks[i], sd, cs[i])
+        toks.append(r["token"])
+        taus.append(r["tau"])
+    return (torch.tensor(toks, dtype=torch.long),
+            torch.tensor(taus, dtype=torch.float32))
+
+
+def sample_tokens(logits, temperature, top_p, top_k, seed, counter):
+    """Seeded temperature / top-k / top-p sampling of each row of
+    `logits` [n, V] (decode_sample.hip on GPU, the fp64 reference on
+    CPU).  Parameters are per-row tensors/lists or scalars; `counter` is
+    the position of the token whose logits these are.  Returns (tokens
+    int64 [n], tau fp32 [n]) — tau is the value threshold of the kept
+    set, -inf when no filter is on or the row is greedy."""
+    if not logits.is_cuda:
+        return sample_tokens_reference(logits, temperature, top_p, top_k,
+                                       seed, counter)
+    C = _require_native("sample_tokens")
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2:
+        raise ValueError("sample_tokens: logits must be bf16 [n, V] on GPU")
+    n = logits.shape[0]
+    blk = pack_samp(n, temperature, top_p, top_k, seed,
+                    counter).to(logits.device)
+    toks, tau = C.sample_tokens(logits.contiguous(), blk[:5], blk[5])
+    return toks, tau
+
+
+def decode_sample_advance(logits, stage, ring, ctr, samp):
+    """decode_advance with seeded sampling: each row's token is drawn
+    from `logits` [b, V] under samp [5, b] (temperature bits, top_p
+    bits, top_k, seed_lo, seed_hi) with Philox counter stage[1], then
+    the same ring store and stage bump as decode_advance
+    (decode_sample.hip).  Rows with temperature 0 take the argmax.
+    GPU-only: the decode graph never runs on CPU."""
+    C = _require_native("decode_sample_advance")
+    C.decode_sample_advance(logits.contiguous(), stage, ring, ctr, samp)
+
+
 def decode_swiglu_down(gu, weight):
     """silu(gate)*up followed by the down projection.  MEASURED
     NEGATIVE as a fused GEMV (skinny_gemm_swiglu kept for reference):

@@ -33,6 +33,7 @@ HIP_SOURCES = [
     "skinny_gemm.hip",
     "wgrad_gemm.hip",
     "decode_fused.hip",
+    "decode_sample.hip",
     "mfma_probe.hip",
 ]
 CPP_SOURCES = ["bindings.cpp"]

@@ -52,6 +52,11 @@ void adamw_mt_launch(const void*, const void*, const void*, const void*,
                      int, float, hipStream_t);
 void decode_advance_launch(const void*, long long, void*, long long,
                            void*, const void*, int, hipStream_t);
+void sample_tokens_launch(const void*, int, long long, const void*,
+                          const void*, void*, void*, hipStream_t);
+void decode_sample_advance_launch(const void*, int, void*, long long, void*,
+                                  const void*, int, const void*,
+                                  hipStream_t);
 void rmsnorm_res_launch(const void*, const void*, const void*, void*, void*,
                         int, int, float, hipStream_t);
 void rope_kvwrite_launch(const void*, void*, void*, void*, const void*,
@@ -541,6 +546,72 @@ void decode_advance(torch::Tensor logits, torch::Tensor stage,
                         (int)ring.size(0), cur_stream());
 }
 
+// ---- seeded decode sampling (decode_sample.hip) ---------------------------
+// The kernel sums 2^40-scaled 64-bit weights, at most V * 2^40 per row:
+// V <= 2^23 keeps every sum below 2^63.
+static const long long kSampleMaxV = 1ll << 23;
+
+std::vector<torch::Tensor> sample_tokens(torch::Tensor logits,
+                                         torch::Tensor samp,
+                                         torch::Tensor counter) {
+  CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
+  CHECK_GPU(samp); CHECK_CONTIG(samp);
+  CHECK_GPU(counter); CHECK_CONTIG(counter);
+  TORCH_CHECK(logits.dim() == 2, "sample_tokens: logits must be [n, V]");
+  TORCH_CHECK(samp.dtype() == torch::kInt32, "sample_tokens: samp int32");
+  TORCH_CHECK(counter.dtype() == torch::kInt32,
+              "sample_tokens: counter int32");
+  const long long n = logits.size(0);
+  const long long V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= kSampleMaxV,
+              "sample_tokens: V must be in [1, 2^23], got ", V);
+  TORCH_CHECK(samp.dim() == 2 && samp.size(0) == 5 && samp.size(1) == n,
+              "sample_tokens: samp must be [5, n]");
+  TORCH_CHECK(counter.dim() == 1 && counter.size(0) == n,
+              "sample_tokens: counter must be [n]");
+  auto tokens = torch::empty({n}, logits.options().dtype(torch::kInt64));
+  auto tau = torch::empty({n}, logits.options().dtype(torch::kFloat));
+  if (n > 0)
+    sample_tokens_launch(logits.data_ptr(), (int)V, n, samp.data_ptr(),
+                         counter.data_ptr(), tokens.data_ptr(),
+                         tau.data_ptr(), cur_stream());
+  return {tokens, tau};
+}
+
+void decode_sample_advance(torch::Tensor logits, torch::Tensor stage,
+                           torch::Tensor ring, torch::Tensor ctr,
+                           torch::Tensor samp) {
+  // seeded sampling + in-graph decode state bump (decode_sample.hip)
+  CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
+  CHECK_GPU(stage); CHECK_CONTIG(stage);
+  CHECK_GPU(ring); CHECK_CONTIG(ring);
+  CHECK_GPU(ctr); CHECK_CONTIG(ctr);
+  CHECK_GPU(samp); CHECK_CONTIG(samp);
+  TORCH_CHECK(stage.dtype() == torch::kInt32,
+              "decode_sample_advance: stage int32");
+  TORCH_CHECK(ring.dtype() == torch::kInt64,
+              "decode_sample_advance: ring int64");
+  TORCH_CHECK(ctr.dtype() == torch::kInt64 && ctr.numel() == 1,
+              "decode_sample_advance: ctr int64 [1]");
+  TORCH_CHECK(samp.dtype() == torch::kInt32,
+              "decode_sample_advance: samp int32");
+  const long long V = logits.size(-1);
+  TORCH_CHECK(V >= 1 && V <= kSampleMaxV,
+              "decode_sample_advance: V must be in [1, 2^23], got ", V);
+  const long long b = logits.numel() / V;
+  TORCH_CHECK(stage.dim() == 2 && stage.size(0) == 6 && stage.size(1) == b,
+              "decode_sample_advance: stage must be [6, b]");
+  TORCH_CHECK(samp.dim() == 2 && samp.size(0) == 5 && samp.size(1) == b,
+              "decode_sample_advance: samp must be [5, b]");
+  TORCH_CHECK(ring.dim() == 2 && ring.size(0) >= 1 && ring.size(1) == b,
+              "decode_sample_advance: ring must be [chunk, b]");
+  if (b > 0)
+    decode_sample_advance_launch(logits.data_ptr(), (int)V, stage.data_ptr(),
+                                 b, ring.data_ptr(), ctr.data_ptr(),
+                                 (int)ring.size(0), samp.data_ptr(),
+                                 cur_stream());
+}
+
 torch::Tensor rope_kvwrite(torch::Tensor qkv, torch::Tensor kc,
                            torch::Tensor vc, torch::Tensor cos_tab,
                            torch::Tensor sin_tab, torch::Tensor positions,
@@ -648,6 +719,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_res", &rmsnorm_res);
   m.def("rope_kvwrite", &rope_kvwrite);
   m.def("decode_advance", &decode_advance);
+  m.def("sample_tokens", &sample_tokens);
+  m.def("decode_sample_advance", &decode_sample_advance);
   m.def("attn_decode_qkv", &attn_decode_qkv);
   m.def("skinny_gemm_fp8_norm", &skinny_gemm_fp8_norm);
   m.def("swiglu_fwd", &swiglu_fwd);

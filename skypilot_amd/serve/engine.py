@@ -11,11 +11,20 @@ With ``prefill_chunk`` set, prompts are prefilled in chunks of that many
 tokens through the append-attention kernel (ops.attn_append), one chunk
 forward per loop iteration between decode steps, so a running stream
 waits for one chunk and never for a whole prompt.
+
+With ``device_sampling`` set, tokens are drawn by the seeded sampling
+kernel (ops.sample_tokens / ops.decode_sample_advance: temperature,
+top-k, top-p, a per-request seed) instead of the host's torch sampler:
+sampled requests then chain graph replays like greedy ones, and a
+request's token at a position depends only on its seed, the position
+and the logits.
 """
 from __future__ import annotations
 
+import math
 import os
 import queue
+import random
 import threading
 import time
 import uuid
@@ -63,6 +72,12 @@ class Request:
     max_tokens: int = 64
     temperature: float = 0.0
     top_p: float = 1.0
+    # top_k <= 0 turns the filter off.  top_k and seed need
+    # Engine(device_sampling=True): there submit() fills in a random seed
+    # when none is given, so a response can report the one that was
+    # used; without it submit() rejects a request that sets either.
+    top_k: int = 0
+    seed: Optional[int] = None
     stop_id: Optional[int] = None
     stream_queue: Optional["queue.Queue"] = None  # per-token streaming
     id: str = field(default_factory=lambda: uuid.uuid4().hex[:12])
@@ -87,7 +102,8 @@ class Engine:
                  hbm_budget_gb: Optional[float] = None,
                  use_graphs: bool = True, model=None, tp_group=None,
                  tp_rank: int = 0, tp_world: int = 1,
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None,
+                 device_sampling: bool = False):
         # Chunked prefill: None keeps whole-prompt prefills (_prefill).
         # The append kernel tiles the chunk by 64 rows.
         if prefill_chunk is not None and (
@@ -98,6 +114,9 @@ class Engine:
                 "prefill_chunk must be None or a positive multiple of 64, "
                 f"got {prefill_chunk!r}")
         self.prefill_chunk = prefill_chunk
+        # False keeps the host sampler (_sample: torch's generator, one
+        # replay per host sync for sampled batches).
+        self.device_sampling = bool(device_sampling)
         self.prefilling: List[_Prefilling] = []
         self.device = torch.device(device or (
             "cuda" if torch.cuda.is_available() else "cpu"))
@@ -193,6 +212,7 @@ class Engine:
 
     # ------------------------------------------------------------------
     def submit(self, req: Request) -> Request:
+        self._check_sampling(req)
         if len(req.prompt_ids) >= self.max_seq:
             req.prompt_ids = req.prompt_ids[-(self.max_seq - 1 -
                                               req.max_tokens):]
@@ -200,12 +220,51 @@ class Engine:
         self.pending.put(req)
         return req
 
+    def _check_sampling(self, req: Request) -> None:
+        """Validate and normalise a request's sampling parameters here,
+        once, so that everything past submit() — the engine thread, the
+        graph's parameter block, the TP plan — sees plain finite floats,
+        an int32 top_k and a 63-bit seed.  Raises ValueError."""
+        for name in ("temperature", "top_p"):
+            v = getattr(req, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{name} must be a number, got {v!r}")
+            try:
+                v = float(v)
+            except OverflowError:
+                v = math.inf
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+            setattr(req, name, v)
+        if req.temperature < 0:
+            raise ValueError(
+                f"temperature must be >= 0, got {req.temperature!r}")
+        if isinstance(req.top_k, bool) or not isinstance(req.top_k, int):
+            raise ValueError(f"top_k must be an int, got {req.top_k!r}")
+        # the kernel takes an int32; <= 0 and >= vocabulary both mean off
+        req.top_k = max(0, min(req.top_k, 2 ** 31 - 1))
+        if req.seed is not None and (isinstance(req.seed, bool)
+                                     or not isinstance(req.seed, int)):
+            raise ValueError(f"seed must be an int, got {req.seed!r}")
+        if not self.device_sampling:
+            # the host sampler has neither: refuse rather than drop them
+            if req.top_k > 0 or req.seed is not None:
+                raise ValueError(
+                    "top_k and seed need device sampling "
+                    "(Engine(device_sampling=True) / --device-sampling)")
+            return
+        if req.seed is None:
+            req.seed = random.getrandbits(63)
+        req.seed %= 1 << 63
+
     def generate(self, prompt_ids: List[int], max_tokens: int = 64,
                  temperature: float = 0.0,
-                 timeout: float = 300.0) -> List[int]:
+                 timeout: float = 300.0, top_p: float = 1.0,
+                 top_k: int = 0, seed: Optional[int] = None) -> List[int]:
         req = self.submit(Request(prompt_ids=prompt_ids,
                                   max_tokens=max_tokens,
-                                  temperature=temperature))
+                                  temperature=temperature, top_p=top_p,
+                                  top_k=top_k, seed=seed))
         if not req.done.wait(timeout):
             raise TimeoutError("generation timed out")
         return req.out_ids
@@ -245,8 +304,9 @@ class Engine:
                                prefill_slots=slots, prefill_lens=lens)
         logits = self.model(toks, positions, ctx)
         last = logits[torch.arange(n), torch.tensor(lens) - 1]  # [n, V]
+        first = self._sample_batch(last, reqs, [l - 1 for l in lens])
         for i, (req, slot) in enumerate(zip(reqs, slots)):
-            next_id = self._sample(last[i], req.temperature, req.top_p)
+            next_id = first[i]
             self.cache.lens[slot] = lens[i]
             req.out_ids.append(next_id)
             if req.stream_queue is not None:
@@ -300,13 +360,19 @@ class Engine:
         self._tp_bcast({"op": "append", "slots": slots, "starts": starts,
                         "lens": lens, "chunks": chunks})
         logits = self._append_forward(slots, starts, lens, chunks)
+        ends = [s + l for s, l in zip(starts, lens)]
+        fin = [i for i, e in enumerate(batch)
+               if ends[i] >= len(e.req.prompt_ids)]
+        first = dict(zip(fin, self._sample_batch(
+            logits[fin, 0], [batch[i].req for i in fin],
+            [ends[i] - 1 for i in fin]))) if fin else {}
         for i, e in enumerate(batch):
             e.done += lens[i]
             self.stats["prefill_tokens"] += lens[i]
             if e.done < len(e.req.prompt_ids):
                 continue
             req, slot = e.req, e.slot
-            next_id = self._sample(logits[i, 0], req.temperature, req.top_p)
+            next_id = first[i]
             self.cache.lens[slot] = e.done
             req.out_ids.append(next_id)
             if req.stream_queue is not None:
@@ -337,12 +403,19 @@ class Engine:
         # All six per-step inputs travel as ONE pinned-host -> device
         # copy of an int32 [6, b] block; the unpack (casts/views) is
         # captured inside the graph.  Rows: 0 toks, 1 positions,
-        # 2 slots, 3 pos, 4 kv_lens, 5 slot_i32.
+        # 2 slots, 3 pos, 4 kv_lens, 5 slot_i32.  With device sampling
+        # the block is [11, b]: rows 6..10 are the sampling parameters
+        # (temperature bits, top_p bits, top_k, seed_lo, seed_hi), so
+        # they change between replays without a recapture and ride in
+        # the same copy.
+        rows = 11 if self.device_sampling else 6
         st = {
-            "host": torch.empty(6, b, dtype=torch.int32,
+            "host": torch.zeros(rows, b, dtype=torch.int32,
                                 pin_memory=True),
-            "stage": torch.zeros(6, b, dtype=torch.int32, device=dev),
+            "block": torch.zeros(rows, b, dtype=torch.int32, device=dev),
         }
+        st["stage"] = st["block"][:6]
+        st["samp"] = st["block"][6:]
         st["stage"][2] = self._scratch_slot
         st["stage"][5] = self._scratch_slot
         st["stage"][4] = 1
@@ -377,8 +450,13 @@ class Engine:
             # profiles/r02_fp8_decode_kernel_stats.txt).  The ctr
             # increment stays a separate captured op so the kernel's
             # ring-row read is ordered before it.
-            ops.decode_advance(st["out"][:, 0], st["stage"], st["ring"],
-                               st["ctr"])
+            if self.device_sampling:
+                ops.decode_sample_advance(st["out"][:, 0], st["stage"],
+                                          st["ring"], st["ctr"],
+                                          st["samp"])
+            else:
+                ops.decode_advance(st["out"][:, 0], st["stage"],
+                                   st["ring"], st["ctr"])
             st["ctr"] += 1
         self._graphs[b] = (g, st)
         self.stats["graph_buckets"] = sorted(self._graphs)
@@ -396,8 +474,10 @@ class Engine:
         if self.use_graphs:
             b = self._bucket(n)
             all_greedy = all(r.temperature == 0 for r in reqs)
+            # in-graph sampling chains sampled rows like greedy ones
+            chain = all_greedy or self.device_sampling
             chunk = 1
-            if (all_greedy and self.pending.empty()
+            if (chain and self.pending.empty()
                     and not self.prefilling):
                 rem = min(r.max_tokens - len(r.out_ids) for r in reqs)
                 cap = min(self.max_seq - 2 - l for l in lens)
@@ -405,9 +485,10 @@ class Engine:
             # TP: the plan must go out BEFORE capture — _get_graph's
             # warmup forwards contain all-reduces that need every rank
             # participating (the follower captures on receipt).
+            samp = self._samp_rows(reqs)
             self._tp_bcast({"op": "decode", "graph": True, "bucket": b,
                             "slots": slots, "lens": lens, "toks": tok_l,
-                            "chunk": chunk})
+                            "chunk": chunk, "samp": samp})
             try:
                 g, st = self._get_graph(b)
             except Exception as e:  # capture unsupported -> eager forever
@@ -418,22 +499,10 @@ class Engine:
                       f"to eager decode: {e!r}", file=sys.stderr)
                 self.use_graphs = False
                 return self._decode_step()
-            scr = self._scratch_slot
-            h = st["host"].numpy()
-            h[0, :n] = tok_l
-            h[0, n:] = 0
-            h[1, :n] = lens
-            h[1, n:] = 0
-            h[2, :n] = slots
-            h[2, n:] = scr
-            h[3] = h[1]
-            h[4] = h[1] + 1
-            h[5] = h[2]
-            st["ctr"].zero_()
-            st["stage"].copy_(st["host"], non_blocking=True)
+            self._stage_inputs(st, slots, lens, tok_l, samp)
             for _ in range(chunk):
                 g.replay()
-            if all_greedy:
+            if chain:
                 ring = st["ring"][:chunk, :n].tolist()  # one sync/chunk
                 for t in range(chunk):
                     for i, slot in enumerate(slots):
@@ -452,7 +521,7 @@ class Engine:
         else:
             self._tp_bcast({"op": "decode", "graph": False,
                             "slots": slots, "lens": lens, "toks": tok_l,
-                            "chunk": 1})
+                            "chunk": 1, "samp": self._samp_rows(reqs)})
             toks = torch.tensor([[t] for t in tok_l], dtype=torch.long,
                                 device=self.device)
             slots_t = torch.tensor(slots, dtype=torch.long,
@@ -467,17 +536,21 @@ class Engine:
                 cache=self.cache, mode="decode", slots=slots_t, pos=pos_t,
                 kv_lens=kv_lens, slot_ids_i32=slots_t.int())
             logits = self.model(toks, positions, ctx)  # [n, 1, V]
-        # Greedy rows batch into one argmax + one sync; sampled rows
-        # (temperature > 0) go through _sample individually.  (The
-        # all-greedy graph path already returned above.)
-        greedy_ids = None
-        if all(r.temperature == 0 for r in reqs):
-            greedy_ids = logits[:n, 0].argmax(-1).tolist()
+        # Device sampling draws the whole batch in one kernel call.  On
+        # the host path greedy rows batch into one argmax + one sync and
+        # sampled rows (temperature > 0) go through _sample individually.
+        # (The chained graph path already returned above.)
+        batch_ids = None
+        if self.device_sampling:
+            # counter = position of each row's input token
+            batch_ids = self._sample_batch(logits[:n, 0], reqs, lens)
+        elif all(r.temperature == 0 for r in reqs):
+            batch_ids = logits[:n, 0].argmax(-1).tolist()
         for i, slot in enumerate(slots):
             self.cache.lens[slot] += 1
             req = self.active[slot]
-            if greedy_ids is not None:
-                next_id = greedy_ids[i]
+            if batch_ids is not None:
+                next_id = batch_ids[i]
             else:
                 next_id = self._sample(logits[i, 0], req.temperature,
                                        req.top_p)
@@ -486,6 +559,55 @@ class Engine:
                 req.stream_queue.put(next_id)
             self.stats["tokens_generated"] += 1
             self._maybe_finish(slot, req, next_id)
+
+    def _samp_rows(self, reqs: List[Request]):
+        """Per-row (temperature, top_p, top_k, seed) for the device
+        sampler — what the TP decode plan carries; None when off."""
+        if not self.device_sampling:
+            return None
+        return [(r.temperature, r.top_p, r.top_k, r.seed) for r in reqs]
+
+    def _stage_inputs(self, st, slots, lens, tok_l, samp) -> None:
+        """Fill the pinned host block for one graph step and start its
+        copy to the device (the leader and the TP followers share this).
+        Padding rows point at the scratch slot and are greedy."""
+        n = len(slots)
+        scr = self._scratch_slot
+        h = st["host"].numpy()
+        h[0, :n] = tok_l
+        h[0, n:] = 0
+        h[1, :n] = lens
+        h[1, n:] = 0
+        h[2, :n] = slots
+        h[2, n:] = scr
+        h[3] = h[1]
+        h[4] = h[1] + 1
+        h[5] = h[2]
+        if self.device_sampling:
+            hf = h.view("float32")
+            hu = h.view("uint32")
+            hf[6, :n] = [r[0] for r in samp]
+            hf[7, :n] = [r[1] for r in samp]
+            h[8, :n] = [r[2] for r in samp]
+            hu[9, :n] = [r[3] & 0xFFFFFFFF for r in samp]
+            hu[10, :n] = [r[3] >> 32 for r in samp]
+            h[6:, n:] = 0  # temperature 0: padding rows take the argmax
+        st["ctr"].zero_()
+        st["block"].copy_(st["host"], non_blocking=True)
+
+    def _sample_batch(self, logits: torch.Tensor, reqs: List[Request],
+                      positions: List[int]) -> List[int]:
+        """Next token of each request from `logits` [n, V], the logits
+        of the tokens at `positions`: first tokens after a prefill and
+        every token of the eager decode step."""
+        if not self.device_sampling:
+            return [self._sample(logits[i], r.temperature, r.top_p)
+                    for i, r in enumerate(reqs)]
+        toks, _ = ops.sample_tokens(
+            logits, [r.temperature for r in reqs],
+            [r.top_p for r in reqs], [r.top_k for r in reqs],
+            [r.seed for r in reqs], positions)
+        return toks.tolist()
 
     def _sample(self, logits: torch.Tensor, temperature: float,
                 top_p: float = 1.0) -> int:
@@ -560,22 +682,9 @@ class Engine:
     @torch.no_grad()
     def _follow_decode(self, msg) -> None:
         slots, lens, tok_l = msg["slots"], msg["lens"], msg["toks"]
-        n = len(slots)
         if msg["graph"]:
             g, st = self._get_graph(msg["bucket"])
-            scr = self._scratch_slot
-            h = st["host"].numpy()
-            h[0, :n] = tok_l
-            h[0, n:] = 0
-            h[1, :n] = lens
-            h[1, n:] = 0
-            h[2, :n] = slots
-            h[2, n:] = scr
-            h[3] = h[1]
-            h[4] = h[1] + 1
-            h[5] = h[2]
-            st["ctr"].zero_()
-            st["stage"].copy_(st["host"], non_blocking=True)
+            self._stage_inputs(st, slots, lens, tok_l, msg.get("samp"))
             for _ in range(msg["chunk"]):
                 g.replay()
             torch.cuda.synchronize()

@@ -19,7 +19,7 @@ import time
 from typing import List, Optional
 
 import uvicorn
-from fastapi import FastAPI
+from fastapi import FastAPI, HTTPException
 from pydantic import BaseModel
 
 from skypilot_amd.serve.engine import Engine, Request
@@ -44,6 +44,8 @@ class CompletionRequest(BaseModel):
     max_tokens: int = 64
     temperature: float = 0.0
     top_p: float = 1.0
+    top_k: int = 0
+    seed: Optional[int] = None
     stop: Optional[List[str]] = None
     stream: bool = False
 
@@ -58,6 +60,9 @@ class ChatRequest(BaseModel):
     messages: List[ChatMessage] = []
     max_tokens: int = 64
     temperature: float = 0.0
+    top_p: float = 1.0
+    top_k: int = 0
+    seed: Optional[int] = None
 
 
 def create_app(engine: Engine, model_name: str) -> FastAPI:
@@ -79,12 +84,21 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
         return {"object": "list",
                 "data": [{"id": model_name, "object": "model"}]}
 
-    def _complete(prompt: str, max_tokens: int, temperature: float):
+    def _complete(prompt: str, req):
         ids = tok.encode(prompt)
         t0 = time.time()
-        out = engine.generate(ids, max_tokens=max_tokens,
-                              temperature=temperature)
-        return out, time.time() - t0, len(ids)
+        r = Request(prompt_ids=ids, max_tokens=req.max_tokens,
+                    temperature=req.temperature, top_p=req.top_p,
+                    top_k=req.top_k, seed=req.seed)
+        try:
+            engine.submit(r)
+        except ValueError as e:
+            raise HTTPException(status_code=400, detail=str(e))
+        if not r.done.wait(300.0):
+            raise HTTPException(status_code=504,
+                                detail="generation timed out")
+        # r.seed: the seed the device sampler used (None on the host path)
+        return r.out_ids, time.time() - t0, len(ids), r.seed
 
     @app.post("/v1/completions")
     def completions(req: CompletionRequest):
@@ -98,8 +112,11 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
             r = _Req(prompt_ids=tok.encode(req.prompt),
                      max_tokens=req.max_tokens,
                      temperature=req.temperature, top_p=req.top_p,
-                     stream_queue=q)
-            engine.submit(r)
+                     top_k=req.top_k, seed=req.seed, stream_queue=q)
+            try:
+                engine.submit(r)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
 
             def sse():
                 while True:
@@ -116,8 +133,7 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
                     yield f"data: {_json.dumps(chunk)}\n\n"
 
             return StreamingResponse(sse(), media_type="text/event-stream")
-        out, dt, n_prompt = _complete(req.prompt, req.max_tokens,
-                                      req.temperature)
+        out, dt, n_prompt, seed = _complete(req.prompt, req)
         text = tok.decode(out)
         finish = "length"
         for stop in req.stop or []:
@@ -128,7 +144,7 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
                 break
         return {
             "id": "cmpl-local", "object": "text_completion",
-            "model": model_name,
+            "model": model_name, "seed": seed,
             "choices": [{"index": 0, "text": text,
                          "finish_reason": finish}],
             "usage": {"prompt_tokens": n_prompt,
@@ -140,11 +156,10 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
     @app.post("/v1/chat/completions")
     def chat(req: ChatRequest):
         prompt = "\n".join(f"{m.role}: {m.content}" for m in req.messages)
-        out, dt, n_prompt = _complete(prompt, req.max_tokens,
-                                      req.temperature)
+        out, dt, n_prompt, seed = _complete(prompt, req)
         return {
             "id": "chatcmpl-local", "object": "chat.completion",
-            "model": model_name,
+            "model": model_name, "seed": seed,
             "choices": [{"index": 0,
                          "message": {"role": "assistant",
                                      "content": tok.decode(out)},
@@ -171,6 +186,10 @@ def main():
                          "(a multiple of 64) between decode steps, so a "
                          "long prompt does not stall running streams; "
                          "default: whole-prompt prefill")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="draw tokens with the seeded sampling kernel "
+                         "(needed for top_k and seed; sampled requests "
+                         "chain graph replays like greedy ones)")
     ap.add_argument("--device", default=None)
     ap.add_argument("--fp8-decode", action="store_true",
                     help="quantize weights to rowwise e4m3fn for the "
@@ -201,7 +220,8 @@ def main():
         engine = Engine(args.model, device=device, max_seq=args.max_seq,
                         max_batch=args.max_batch, model=shard,
                         tp_rank=rank, tp_world=args.tp,
-                        prefill_chunk=args.prefill_chunk)
+                        prefill_chunk=args.prefill_chunk,
+                        device_sampling=args.device_sampling)
         if args.fp8_decode:
             engine.enable_fp8_decode()
         if rank > 0:
@@ -217,7 +237,8 @@ def main():
         return
     engine = Engine(args.model, device=args.device, max_seq=args.max_seq,
                     max_batch=args.max_batch,
-                    prefill_chunk=args.prefill_chunk)
+                    prefill_chunk=args.prefill_chunk,
+                    device_sampling=args.device_sampling)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode()
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
