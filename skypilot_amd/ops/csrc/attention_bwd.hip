@@ -378,7 +378,7 @@ extern "C" __global__ __launch_bounds__(256, 1) void attn_bwd_dq_swapped_kernel(
 }
 
 // Backward dispatch: the Dvec preprocess always runs; then S % 128 == 0
-// runs the v3 dkv/dq kernels (dkv_variant picks among the v3 dkv kernels,
+// runs the v3 dkv/dq kernels (dkv_variant and dq_variant pick among them,
 // see attn_bwd_v3_launch) and every other S % 64 == 0 runs the 64-tile
 // kernels above.  They stay because they are the only path for the
 // shapes v3 does not take, such as a sequence padded to 64 rows.
@@ -387,14 +387,15 @@ extern "C" void attn_bwd_launch(const void* Q, const void* K, const void* V,
                                 const float* lse, float* Dvec, void* dQ,
                                 void* dK, void* dV, int B, int S, int Hq,
                                 int Hkv, float scale, bool causal,
-                                int dkv_variant, hipStream_t stream) {
+                                int dkv_variant, int dq_variant,
+                                hipStream_t stream) {
   long long rows = (long long)B * S * Hq;
   hipLaunchKernelGGL(attn_bwd_pre_kernel, dim3(membound_grid(rows, 4)),
                      dim3(256), 0, stream, (const unsigned short*)dO,
                      (const unsigned short*)O, Dvec, rows, S, Hq);
   if (S % 128 == 0) {
     attn_bwd_v3_launch(Q, K, V, dO, lse, Dvec, dQ, dK, dV, B, S, Hq, Hkv,
-                       scale, causal, dkv_variant, stream);
+                       scale, causal, dkv_variant, dq_variant, stream);
     return;
   }
   hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(S / BN, B * Hkv), dim3(256),

@@ -602,8 +602,14 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dq_v3_kernel(
 
   int my_q = qbase + 32 * w + col;
 
-  // Q as B-fragments pre-scaled by scale*log2(e); dO fragments are
-  // re-read from L2 per kv tile (keeping them resident spilled).
+  // Q as B-fragments pre-scaled by scale*log2(e).  The dO fragments are
+  // re-read from L2 in every kv tile, inside the MFMA loop, although they
+  // depend on the q row only: next to this kernel's 32 tr-read and 32
+  // row-fragment address registers, keeping them resident spills (180 B
+  // per lane against the 88 B it has now).  Each of those loads is
+  // followed by a vmcnt(0) that also drains the staging DMAs of the next
+  // tile; attn_bwd_dq_v3p_kernel below rebuilds the addresses and keeps
+  // dO resident.  This kernel stays as the bit-reference (dq_variant 0).
   s16x8 q_b[8];
   float lse2, dvq;
 #define DQ_LOAD_Q()                                                       \
@@ -812,6 +818,305 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dq_v3_kernel(
   DQ_EPILOGUE();
 #undef DQ_EPILOGUE
 #undef DQ_LOAD_Q
+#undef DQ_STAGE
+#undef DQ_TR_ISSUE
+}
+
+// ---------------------------------------------------------------------------
+// Pipelined dq kernel: the grid, LDS tile layouts, MFMA sequence,
+// accumulation order, exponent math and epilogue of attn_bwd_dq_v3_kernel
+// (dQ is bit-identical); only the memory schedule and the register use
+// differ.
+//
+//  * The lane's eight dO fragments depend on its q row only, so they are
+//    loaded once per q tile next to Q/lse/Dvec and stay in 32 VGPRs.  The
+//    tile loop then holds no ordinary global load, and its only vmcnt wait
+//    is the vm_drain() in front of the handoff barrier: the staging DMAs
+//    of tile t+1 stay in flight under all of tile t's MFMAs.
+//  * The staging is unconditional (the block's last iteration restages its
+//    own tile into the free buffer), so no wait has to cover a path
+//    without it.
+//  * One __shared__ array: the two K and two V buffers are compile-time
+//    offsets of each other.  The 32 tr-read addresses are 8 lane bases
+//    plus the DS offset field, the 32 row-fragment addresses one lane base
+//    XOR (ks << 5) plus the offset field; the bases carry the buffer
+//    parity and are flipped in place once per tile.
+// ---------------------------------------------------------------------------
+extern "C" __global__ __launch_bounds__(256, 2) void attn_bwd_dq_v3p_kernel(
+    const unsigned short* __restrict__ Q, const unsigned short* __restrict__ K,
+    const unsigned short* __restrict__ V, const unsigned short* __restrict__ dO,
+    const float* __restrict__ lse, const float* __restrict__ Dvec,
+    unsigned short* __restrict__ dQ, int B, int S, int Hq, int Hkv,
+    float scale, int causal) {
+  // byte offsets: K buffer i at i * 16384, V buffer i at 32768 + i * 16384.
+  __shared__ unsigned short lds[4 * 64 * ATT_D];
+
+  const int nq = S / 128;
+  const bool paired = causal && (int)gridDim.x * 2 == nq;
+  const int qtA = paired ? nq - 1 - (int)blockIdx.x
+                         : (int)gridDim.x - 1 - (int)blockIdx.x;
+  const int qtB = paired ? (int)blockIdx.x : 0;
+  const int bh = blockIdx.y;
+  const int b = bh / Hq;
+  const int qh = bh % Hq;
+  const int kvh = qh / (Hq / Hkv);
+  int qbase = qtA * 128;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int w = tid >> 6;
+  const int col = lane & 31;
+  const int h = lane >> 5;
+  const int g = lane >> 4;
+  const int lw = lane & 15;
+
+  const long long q_rowstride = (long long)Hq * ATT_D;
+  const long long kv_rowstride = (long long)Hkv * ATT_D;
+  const unsigned short* Qb = Q + ((long long)b * S * Hq + qh) * ATT_D;
+  const unsigned short* Kb = K + ((long long)b * S * Hkv + kvh) * ATT_D;
+  const unsigned short* Vb = V + ((long long)b * S * Hkv + kvh) * ATT_D;
+  const unsigned short* dOb = dO + ((long long)b * S * Hq + qh) * ATT_D;
+  const float* lse_b = lse + ((long long)b * Hq + qh) * S;
+  const float* dvec_b = Dvec + ((long long)b * Hq + qh) * S;
+
+  int my_q = qbase + 32 * w + col;
+
+  // Q as B-fragments pre-scaled by scale*log2(e), and the dO B-fragments,
+  // resident for the whole q tile.  The empty asm makes the dO registers
+  // defined here, so their vmcnt wait sits here and not in the tile loop.
+  s16x8 q_b[8], do_b[8];
+  float lse2, dvq;
+#define DQP_LOAD_Q()                                                      \
+  {                                                                       \
+    const float qs = scale * 1.44269504088896340736f;                     \
+    const unsigned short* src = Qb + (long long)my_q * q_rowstride;       \
+    const unsigned short* dsrc = dOb + (long long)my_q * q_rowstride;     \
+    _Pragma("unroll") for (int ks = 0; ks < 8; ++ks)                      \
+      do_b[ks] = *(const s16x8*)(dsrc + ks * 16 + h * 8);                 \
+    _Pragma("unroll") for (int ks = 0; ks < 8; ++ks) {                    \
+      s16x8 raw = *(const s16x8*)(src + ks * 16 + h * 8);                 \
+      _Pragma("unroll") for (int j = 0; j < 8; ++j)                       \
+        raw[j] = (short)f2bf(bf2f((unsigned short)raw[j]) * qs);          \
+      q_b[ks] = raw;                                                      \
+    }                                                                     \
+    float lv = lse_b[my_q];                                               \
+    lse2 = (lv == -INFINITY) ? 3.0e37f                                    \
+                             : lv * 1.44269504088896340736f;              \
+    dvq = dvec_b[my_q];                                                   \
+    _Pragma("unroll") for (int ks = 0; ks < 8; ++ks)                      \
+      asm volatile("" : "+v"(do_b[ks]));                                  \
+    asm volatile("" : "+v"(lse2), "+v"(dvq));                             \
+  }
+
+  f32x16 dq_acc[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dq_acc[dt][r] = 0.f;
+
+  const int nt_A = causal ? (qbase + 128) / 64 : S / 64;
+  const int nt_B = paired ? (qtB * 128 + 128) / 64 : 0;
+  const int total_t = nt_A + nt_B;
+  int w_tiles = causal ? ((qbase + 32 * w + 31) >> 6) + 1 : nt_A;
+
+#define DQP_EPILOGUE()                                                    \
+  {                                                                       \
+    unsigned short* dQb = dQ + ((long long)b * S * Hq + qh) * ATT_D;      \
+    unsigned short* qrow = dQb + (long long)my_q * q_rowstride;           \
+    _Pragma("unroll") for (int dt = 0; dt < 4; ++dt)                      \
+      _Pragma("unroll") for (int rq = 0; rq < 4; ++rq) {                  \
+        s16x4 ov;                                                         \
+        _Pragma("unroll") for (int r = 0; r < 4; ++r)                     \
+          ov[r] = (short)f2bf(dq_acc[dt][rq * 4 + r] * scale);            \
+        *(s16x4*)(qrow + dt * 32 + rq * 8 + h * 4) = ov;                  \
+      }                                                                   \
+  }
+
+  // Staging: wave w stages rows [16w, 16w+16) of both K and V via 4 + 4
+  // global_load_lds (linear dest, pre-swizzled source) from a wave-uniform
+  // tile base plus a 32-bit lane offset.  Row 16w + 4i + g of the tile,
+  // chunk lw ^ (4i + g): i moves the row by 4 and flips chunk bits 2..3.
+  const unsigned kv_rs2 = (unsigned)kv_rowstride * 2u;  // row stride, bytes
+  const unsigned sg_off =
+      (unsigned)(16 * w + g) * kv_rs2 + (unsigned)((lw ^ g) << 4);
+#define DQP_STAGE(kvrow0, bufi)                                           \
+  {                                                                       \
+    gptr_t ksrc = uniform_ptr(Kb + (long long)(kvrow0) * kv_rowstride);   \
+    gptr_t vsrc = uniform_ptr(Vb + (long long)(kvrow0) * kv_rowstride);   \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                       \
+      const unsigned off = (sg_off ^ (unsigned)(i << 6)) + 4u * i * kv_rs2; \
+      char* dst = (char*)lds + (bufi) * 16384 + (16 * w + 4 * i) * 256;   \
+      gload_lds16(ksrc + off, dst);                                       \
+      gload_lds16(vsrc + off, dst + 32768);                               \
+    }                                                                     \
+  }
+
+  // Lane bases inside the K buffer, initialised for buffer 1 and flipped
+  // at the top of every tile (so tile 0 reads buffer 0).
+  //  * tra: the eight tr-read addresses of k-step 0; k-step ks moves kv_s
+  //    by 16 rows = +4096 B and leaves the swizzle key kv_s & 15 alone.
+  //  * frag: swzK16(col*256 + h*16, col), the row-fragment address of
+  //    k-step 0 for n = 0; k-step ks is ^ (ks << 5), n = 1 is +8192 (the
+  //    key (32 + col) & 15 is the same) and V is +32768.
+  unsigned tra[8];
+  {
+    const int kv_s = ((g >> 1) << 3) + (lw >> 2);
+    const int d_s0 = ((g & 1) << 4) + ((lw & 3) << 2);
+    const unsigned base = (unsigned)(size_t)((char*)lds) + 16384u;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int kv = kv_s + 4 * (i & 1);
+      const int d = 32 * (i >> 1) + d_s0;
+      tra[i] = base + (unsigned)(kv * 256 + (((d >> 3) ^ (kv & 15)) << 4) +
+                                 ((d & 7) << 1));
+    }
+  }
+  unsigned frag = (unsigned)swzK16(col * 256 + h * 16, col) + 16384u;
+
+  DQP_LOAD_Q();
+  DQP_STAGE(0, 0);
+
+  for (int it = 0; it < total_t; ++it) {
+    if (paired && it == nt_A) {
+      DQP_EPILOGUE();
+      qbase = qtB * 128;
+      my_q = qbase + 32 * w + col;
+      DQP_LOAD_Q();
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dq_acc[dt][r] = 0.f;
+      w_tiles = ((qbase + 32 * w + 31) >> 6) + 1;
+    }
+    const int kt = it < nt_A ? it : it - nt_A;
+    const int buf = it & 1;
+    {
+      const unsigned flip = buf ? 16384u : (unsigned)-16384;
+      frag += flip;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) tra[i] += flip;
+    }
+    vm_drain();  // the only vmcnt wait of the loop: the DMA of this
+                 // buffer, issued a whole tile ago
+    __syncthreads();
+    {
+      // next tile, or on the block's last iteration this tile again (a
+      // row range already read, into the free buffer).
+      const int nx = it + 1 < total_t ? it + 1 : it;
+      const int kt2 = nx < nt_A ? nx : nx - nt_A;
+      DQP_STAGE(kt2 * 64, buf ^ 1);
+    }
+    if (kt >= w_tiles) continue;
+
+    const int kvbase = kt * 64;
+    // ---- S^T = K' Q^T and dP^T = V dO^T (4 interleaved chains).
+    f32x16 st[2], dpt[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        st[n][r] = 0.f;
+        dpt[n][r] = 0.f;
+      }
+    // The fragment address is rebuilt per k-step by one XOR; the empty
+    // asm keeps the eight results from being hoisted into registers.
+    unsigned fr = frag;
+    asm volatile("" : "+v"(fr));
+    // MFMA i = 4 ks + 2 n + (0: S chain, 1: dP chain) takes fragment i
+    // (K or V rows n*32 + col, k-step ks).  The reads are split-phase
+    // like the tr reads: four fragments (the two K/V pairs of one k-step)
+    // are in flight ahead of the MFMA that consumes them, each MFMA is
+    // followed by the read of the fragment four later into the registers
+    // it has just consumed, and every wait is a counted lgkmcnt(3).
+    // (With plain C++ loads hipcc waits lgkmcnt(0) here: while a
+    // global_load_lds is outstanding it treats the LGKM counter as
+    // unordered.)
+    s16x8 fa[4];
+#define DQP_RD(i)                                                         \
+  ds_read128_issue_off<(((i) >> 1) & 1) * 8192 + ((i) & 1) * 32768>(      \
+      &fa[(i) & 3], fr ^ (unsigned)(((i) >> 2) << 5))
+#define DQP_STEP(i)                                                       \
+  {                                                                       \
+    lgkm_wait_bind1<((i) < 28 ? 3 : 31 - (i))>(&fa[(i) & 3]);             \
+    if ((i) & 1)                                                          \
+      dpt[((i) >> 1) & 1] =                                               \
+          MFMA32V3(as_bf16x8(fa[(i) & 3]), as_bf16x8(do_b[(i) >> 2]),     \
+                   dpt[((i) >> 1) & 1]);                                  \
+    else                                                                  \
+      st[((i) >> 1) & 1] =                                                \
+          MFMA32V3(as_bf16x8(fa[(i) & 3]), as_bf16x8(q_b[(i) >> 2]),      \
+                   st[((i) >> 1) & 1]);                                   \
+    __builtin_amdgcn_sched_barrier(0);                                    \
+    if ((i) + 4 < 32) DQP_RD((i) + 4);                                    \
+  }
+#define DQP_STEP4(i)                                                      \
+  DQP_STEP(i) DQP_STEP((i) + 1) DQP_STEP((i) + 2) DQP_STEP((i) + 3)
+    __builtin_amdgcn_s_setprio(1);
+    DQP_RD(0);
+    DQP_RD(1);
+    DQP_RD(2);
+    DQP_RD(3);
+    DQP_STEP4(0) DQP_STEP4(4) DQP_STEP4(8) DQP_STEP4(12)
+    DQP_STEP4(16) DQP_STEP4(20) DQP_STEP4(24) DQP_STEP4(28)
+    __builtin_amdgcn_s_setprio(0);
+#undef DQP_STEP4
+#undef DQP_STEP
+#undef DQP_RD
+
+    // ---- P^T = exp2(S' - lse'); dS^T = P^T * (dP^T - Dvec[q]).
+    if (causal && kvbase + 63 > qbase + 32 * w) {
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          int kv = kvbase + n * 32 + (r & 3) + ((r >> 2) << 3) + (h << 2);
+          if (kv > my_q) st[n][r] = -30000.f;
+        }
+    }
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float p = exp2f(st[n][r] - lse2);
+        dpt[n][r] = p * (dpt[n][r] - dvq);
+      }
+
+    // ---- dQ^T += K^T dS^T: A = tr reads of the K tile (column
+    // fragments over the swizzled layout), B = permlane pack of dS^T.
+    tr4 t0, t1;
+    s16x8 db;
+#define DQP_TR_ISSUE(ks)                                                  \
+  {                                                                       \
+    ds_tr4_issue_off_ec<(ks) * 4096>(&t0, tra[0], tra[1], tra[2], tra[3]); \
+    ds_tr4_issue_off_ec<(ks) * 4096>(&t1, tra[4], tra[5], tra[6], tra[7]); \
+  }
+    DQP_TR_ISSUE(0);
+    V3_PACK2(db, dpt, 0);
+    lgkm_wait0_bind2(&t0, &t1);
+    DQ_MFMA(db);
+    DQP_TR_ISSUE(1);
+    V3_PACK2(db, dpt, 1);
+    lgkm_wait0_bind2(&t0, &t1);
+    DQ_MFMA(db);
+    DQP_TR_ISSUE(2);
+    V3_PACK2(db, dpt, 2);
+    lgkm_wait0_bind2(&t0, &t1);
+    DQ_MFMA(db);
+    DQP_TR_ISSUE(3);
+    V3_PACK2(db, dpt, 3);
+    lgkm_wait0_bind2(&t0, &t1);
+    DQ_MFMA(db);
+  }
+  // The last iteration's restaging is still in flight: it must land
+  // before the block gives its LDS back.
+  vm_drain();
+
+  DQP_EPILOGUE();
+#undef DQP_EPILOGUE
+#undef DQP_LOAD_Q
+#undef DQP_STAGE
+#undef DQP_TR_ISSUE
+#undef DQ_MFMA
 }
 
 // dkv_variant: 0 = attn_bwd_dkv_v3_kernel, 1 = the pipelined kernel,
@@ -824,7 +1129,7 @@ extern "C" void attn_bwd_v3_launch(const void* Q, const void* K,
                                    void* dQ, void* dK, void* dV, int B,
                                    int S, int Hq, int Hkv, float scale,
                                    bool causal, int dkv_variant,
-                                   hipStream_t stream) {
+                                   int dq_variant, hipStream_t stream) {
   const int variant = dkv_variant >= 0 ? dkv_variant : 2;
   if (variant == 0) {
     dim3 gkv(S / 128, B * Hkv);
@@ -847,7 +1152,12 @@ extern "C" void attn_bwd_v3_launch(const void* Q, const void* K,
   int nqq = S / 128;
   int gqx = (causal && nqq % 2 == 0) ? nqq / 2 : nqq;
   dim3 gq(gqx, B * Hq);
-  hipLaunchKernelGGL(attn_bwd_dq_v3_kernel, gq, dim3(256), 0, stream,
+  // dq_variant: 0 = attn_bwd_dq_v3_kernel, 1 = the pipelined kernel;
+  // -1 = 1, the shipped choice.  Measured per call at B6 S4096 Hq32 Hkv8
+  // causal: 2.25 / 1.31 ms, dQ bit-identical (docs/BENCHMARKS.md).
+  const int dqv = dq_variant >= 0 ? dq_variant : 1;
+  hipLaunchKernelGGL(dqv == 1 ? attn_bwd_dq_v3p_kernel : attn_bwd_dq_v3_kernel,
+                     gq, dim3(256), 0, stream,
                      (const unsigned short*)Q, (const unsigned short*)K,
                      (const unsigned short*)V, (const unsigned short*)dO,
                      lse, Dvec, (unsigned short*)dQ, B, S, Hq, Hkv, scale,

@@ -23,7 +23,7 @@ void attn_bwd_launch(const void* Q, const void* K, const void* V,
                      const void* O, const void* dO, const float* lse,
                      float* Dvec, void* dQ, void* dK, void* dV, int B, int S,
                      int Hq, int Hkv, float scale, bool causal,
-                     int dkv_variant, hipStream_t stream);
+                     int dkv_variant, int dq_variant, hipStream_t stream);
 
 // v3 kernels: forward needs S % 256 == 0, backward S % 128 == 0.
 void attn_fwd_v3_launch(const void* Q, const void* K, const void* V, void* O,
@@ -33,5 +33,5 @@ void attn_bwd_v3_launch(const void* Q, const void* K, const void* V,
                         const void* dO, const float* lse, const float* Dvec,
                         void* dQ, void* dK, void* dV, int B, int S, int Hq,
                         int Hkv, float scale, bool causal, int dkv_variant,
-                        hipStream_t stream);
+                        int dq_variant, hipStream_t stream);
 }

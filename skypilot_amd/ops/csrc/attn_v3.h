@@ -80,9 +80,55 @@ __device__ __forceinline__ void ds_tr4_issue_off(tr4* t, unsigned a0,
       : "memory");
 }
 
+// ds_tr4_issue_off with early-clobber outputs: no result register may
+// double as the address of a later read of the same group (the data
+// return of one read could otherwise overwrite it before that read
+// issues).
+template <int OFF>
+__device__ __forceinline__ void ds_tr4_issue_off_ec(tr4* t, unsigned a0,
+                                                    unsigned a1, unsigned a2,
+                                                    unsigned a3) {
+  static_assert(OFF >= 0 && OFF < 65536, "DS offset field is 16 bits");
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %4 offset:%8\n\t"
+      "ds_read_b64_tr_b16 %1, %5 offset:%8\n\t"
+      "ds_read_b64_tr_b16 %2, %6 offset:%8\n\t"
+      "ds_read_b64_tr_b16 %3, %7 offset:%8"
+      : "=&v"(t->d[0]), "=&v"(t->d[1]), "=&v"(t->d[2]), "=&v"(t->d[3])
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "n"(OFF)
+      : "memory");
+}
+
+// Split-phase 16 B LDS read at lane address + compile-time offset, and the
+// counted wait that binds the dependency to its destination: at most N
+// younger LDS reads may still be in flight.  The caller pins the order of
+// the consumers with sched_barrier, as for the tr reads.
+template <int OFF>
+__device__ __forceinline__ void ds_read128_issue_off(s16x8* d, unsigned a) {
+  static_assert(OFF >= 0 && OFF < 65536, "DS offset field is 16 bits");
+  asm volatile("ds_read_b128 %0, %1 offset:%2"
+               : "=&v"(*d)
+               : "v"(a), "n"(OFF)
+               : "memory");
+}
+template <int N>
+__device__ __forceinline__ void lgkm_wait_bind1(s16x8* d) {
+  static_assert(N >= 0 && N < 16, "lgkmcnt is 4 bits");
+  asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(*d) : "n"(N) : "memory");
+  __builtin_amdgcn_sched_barrier(0);
+}
+
 // Async 16B global->LDS copy: per-lane global source, wave-uniform LDS
 // base + lane*16 destination (guide §5: the only supported dest form).
 __device__ __forceinline__ void gload_lds16(const void* g, void* l) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) unsigned int*)g,
+      (__attribute__((address_space(3))) unsigned int*)l, 16, 0, 0);
+}
+// The same from a global-address-space pointer (scalar base + 32-bit lane
+// offset sources keep their addressing form).
+__device__ __forceinline__ void gload_lds16(
+    const __attribute__((address_space(1))) char* g, void* l) {
   __builtin_amdgcn_global_load_lds(
       (const __attribute__((address_space(1))) unsigned int*)g,
       (__attribute__((address_space(3))) unsigned int*)l, 16, 0, 0);

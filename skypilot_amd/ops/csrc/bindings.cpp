@@ -239,12 +239,17 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor Q, torch::Tensor K,
                                     torch::Tensor V, torch::Tensor O,
                                     torch::Tensor dO, torch::Tensor lse,
                                     double scale, bool causal,
-                                    int64_t dkv_variant) {
+                                    int64_t dkv_variant,
+                                    int64_t dq_variant) {
   // dkv_variant: -1 = default (the shipped kernel, 2); 0 = v3 dkv,
   // 1 = pipelined v3 dkv, 2 = pipelined + heavy-first grid.
+  // dq_variant: -1 = default (the shipped kernel); 0 = v3 dq,
+  // 1 = pipelined v3 dq.
   check_attn_qkv("attn_bwd", Q, K, V);
   TORCH_CHECK(dkv_variant >= -1 && dkv_variant <= 2,
               "attn_bwd: dkv_variant must be -1, 0, 1 or 2");
+  TORCH_CHECK(dq_variant >= -1 && dq_variant <= 1,
+              "attn_bwd: dq_variant must be -1, 0 or 1");
   const int B = (int)Q.size(0), S = (int)Q.size(1), Hq = (int)Q.size(2);
   const int Hkv = (int)K.size(2);
   const torch::Tensor* outs[] = {&O, &dO};
@@ -274,7 +279,7 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor Q, torch::Tensor K,
                   dO.data_ptr(), lse.data_ptr<float>(),
                   Dvec.data_ptr<float>(), dQ.data_ptr(), dK.data_ptr(),
                   dV.data_ptr(), B, S, Hq, Hkv, (float)scale, causal,
-                  (int)dkv_variant, cur_stream());
+                  (int)dkv_variant, (int)dq_variant, cur_stream());
   return {dQ, dK, dV};
 }
 
@@ -706,7 +711,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd);
   m.def("attn_bwd", &attn_bwd, py::arg("Q"), py::arg("K"), py::arg("V"),
         py::arg("O"), py::arg("dO"), py::arg("lse"), py::arg("scale"),
-        py::arg("causal"), py::arg("dkv_variant") = -1);
+        py::arg("causal"), py::arg("dkv_variant") = -1,
+        py::arg("dq_variant") = -1);
   m.def("attn_decode", &attn_decode);
   m.def("attn_append", &attn_append);
   m.def("skinny_gemm", &skinny_gemm);
