@@ -478,8 +478,9 @@ def decode_norm_linear(x, res, norm_w, eps, weight):
             res2 = (res.reshape(n, i).contiguous() if res is not None
                     else torch.empty(0, dtype=x.dtype, device=x.device))
             x2, y = C.skinny_gemm_fp8_norm(
-                x.reshape(n, i).contiguous(), res2, norm_w, eps,
-                ent[0], ent[1], res is not None)
+                x.reshape(n, i).contiguous(), res2,
+                norm_w.to(x.dtype).contiguous(), eps, ent[0], ent[1],
+                res is not None)
             return x2.view(*lead, i), y.view(*lead, o)
     if res is None:
         return x, decode_linear(rmsnorm(x, norm_w, eps), weight)
@@ -492,8 +493,9 @@ def rmsnorm_res(x, res, weight, eps: float = 1e-5):
     kernel instead of add + norm; decode_fused.hip).  No autograd."""
     if x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] % 256 == 0:
         C = _require_native("rmsnorm_res")
-        x2, h = C.rmsnorm_res(x.contiguous(), res.contiguous(), weight,
-                              eps)
+        # the kernel reads bf16 weights; .to() of a bf16 weight is a no-op
+        x2, h = C.rmsnorm_res(x.contiguous(), res.contiguous(),
+                              weight.to(x.dtype).contiguous(), eps)
         return x2, h
     x2 = (x + res)
     return x2, rmsnorm(x2, weight, eps)

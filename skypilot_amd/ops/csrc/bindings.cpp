@@ -8,6 +8,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <limits>
 #include <vector>
 
 #include "attn_append.h"
@@ -283,20 +284,116 @@ std::vector<torch::Tensor> attn_bwd(torch::Tensor Q, torch::Tensor K,
   return {dQ, dK, dV};
 }
 
+// ---- argument checks of the decode-step bindings --------------------------
+// The decode kernels index every tensor as dense memory of one fixed
+// element type, so each tensor argument is checked here for device,
+// dtype, contiguity, rank and shape before anything is launched; `op`
+// and `name` go into the message.  VALUES held in device memory (slot
+// ids, positions, kv lengths) are NOT validated: reading them back would
+// put a host sync into the captured decode graph.  The caller owns them:
+// 0 <= slot < slots, 0 <= position < S_max, 0 <= kv_len <= S_max.
+static void check_dense(const char* op, const char* name,
+                        const torch::Tensor& t, at::ScalarType dtype,
+                        const torch::Tensor& first) {
+  TORCH_CHECK(t.defined(), op, ": ", name, " must be a tensor");
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on GPU");
+  TORCH_CHECK(t.device() == first.device(), op, ": ", name, " is on ",
+              t.device(), " but the first tensor is on ", first.device());
+  TORCH_CHECK(t.scalar_type() == dtype, op, ": ", name, " must be ", dtype,
+              ", got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name,
+              " must be contiguous, got sizes ", t.sizes(), " strides ",
+              t.strides());
+}
+
+// Kc / Vc: dense bf16 [slots, S_max, Hkv, 128] of one shape.
+static void check_kv_cache(const char* op, const torch::Tensor& Kc,
+                           const torch::Tensor& Vc, int64_t Hq, int64_t Hkv,
+                           const torch::Tensor& first) {
+  const torch::Tensor* ts[] = {&Kc, &Vc};
+  const char* names[] = {"Kc", "Vc"};
+  for (int i = 0; i < 2; ++i) {
+    check_dense(op, names[i], *ts[i], at::kBFloat16, first);
+    TORCH_CHECK(ts[i]->dim() == 4, op, ": ", names[i],
+                " must be [slots, S_max, Hkv, 128], got ", ts[i]->dim(),
+                " dims");
+    TORCH_CHECK(ts[i]->size(3) == ATT_D, op, ": ", names[i],
+                " head dim must be 128, got ", ts[i]->size(3));
+  }
+  TORCH_CHECK(Vc.sizes() == Kc.sizes(), op, ": Vc must have Kc's shape ",
+              Kc.sizes(), ", got ", Vc.sizes());
+  TORCH_CHECK(Kc.size(0) > 0 && Kc.size(1) > 0 &&
+                  Kc.size(1) <= std::numeric_limits<int>::max(),
+              op, ": Kc must hold at least one slot and one row, got ",
+              Kc.sizes());
+  TORCH_CHECK(Hkv > 0 && Hkv == Kc.size(2), op, ": Hkv = ", Hkv,
+              " must equal Kc.size(2) = ", Kc.size(2));
+  TORCH_CHECK(Hq > 0 && Hq % Hkv == 0, op, ": Hq = ", Hq,
+              " must be a positive multiple of Hkv = ", Hkv);
+}
+
+// One int32 entry per sequence, on the device.
+static void check_index(const char* op, const char* name,
+                        const torch::Tensor& t, int64_t B,
+                        const torch::Tensor& first) {
+  check_dense(op, name, t, at::kInt, first);
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == B, op, ": ", name,
+              " must be a [B] = [", B, "] tensor, got ", t.sizes());
+}
+
+// cos / sin: fp32 [rows >= S_max, 64], row p for position p.
+static void check_rope_tables(const char* op, const torch::Tensor& cos_tab,
+                              const torch::Tensor& sin_tab, int64_t S_max,
+                              const torch::Tensor& first) {
+  const torch::Tensor* ts[] = {&cos_tab, &sin_tab};
+  const char* names[] = {"cos", "sin"};
+  for (int i = 0; i < 2; ++i) {
+    check_dense(op, names[i], *ts[i], at::kFloat, first);
+    TORCH_CHECK(ts[i]->dim() == 2 && ts[i]->size(1) == ATT_D / 2, op, ": ",
+                names[i], " must be [rows, 64], got ", ts[i]->sizes());
+    TORCH_CHECK(ts[i]->size(0) >= S_max, op, ": ", names[i], " has ",
+                ts[i]->size(0), " rows, fewer than the cache's S_max = ",
+                S_max);
+  }
+}
+
+// One block per (sequence, q head) in grid.x.
+static void check_grid(const char* op, int64_t B, int64_t Hq) {
+  TORCH_CHECK(B * Hq <= std::numeric_limits<int>::max(), op, ": B * Hq = ",
+              B * Hq, " exceeds the grid limit 2^31 - 1");
+}
+
+// The packed [B, (Hq + 2 Hkv) * 128] q|k|v rows of a decode step.
+static void check_packed_qkv(const char* op, const torch::Tensor& qkv,
+                             int64_t Hq, int64_t Hkv) {
+  check_dense(op, "qkv", qkv, at::kBFloat16, qkv);
+  TORCH_CHECK(Hq > 0 && Hkv > 0, op, ": Hq = ", Hq, " and Hkv = ", Hkv,
+              " must be positive");
+  TORCH_CHECK(qkv.dim() == 2 && qkv.size(1) == (Hq + 2 * Hkv) * ATT_D, op,
+              ": qkv must be [B, (Hq + 2 * Hkv) * 128] = [B, ",
+              (Hq + 2 * Hkv) * ATT_D, "], got ", qkv.sizes());
+}
+
 torch::Tensor attn_decode(torch::Tensor Q, torch::Tensor Kc,
                           torch::Tensor Vc, torch::Tensor kv_lens,
                           torch::Tensor slot_ids, double scale) {
-  CHECK_GPU(Q); CHECK_CONTIG(Q); CHECK_BF16(Q);
-  TORCH_CHECK(kv_lens.scalar_type() == at::kInt);
-  TORCH_CHECK(slot_ids.scalar_type() == at::kInt);
-  const int B = (int)Q.size(0), Hq = (int)Q.size(1), D = (int)Q.size(2);
+  // decode attention over the slot KV cache (attention_decode.hip)
+  const char* op = "attn_decode";
+  check_dense(op, "Q", Q, at::kBFloat16, Q);
+  TORCH_CHECK(Q.dim() == 3 && Q.size(2) == ATT_D, op,
+              ": Q must be [B, Hq, 128], got ", Q.sizes());
+  const int64_t B = Q.size(0), Hq = Q.size(1);
+  check_kv_cache(op, Kc, Vc, Hq, Kc.dim() == 4 ? Kc.size(2) : 0, Q);
+  check_index(op, "kv_lens", kv_lens, B, Q);
+  check_index(op, "slot_ids", slot_ids, B, Q);
+  check_grid(op, B, Hq);
   const int S_max = (int)Kc.size(1), Hkv = (int)Kc.size(2);
-  TORCH_CHECK(D == 128);
   auto O = torch::empty_like(Q);
-  attn_decode_launch(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
-                     O.data_ptr(), kv_lens.data_ptr<int>(),
-                     slot_ids.data_ptr<int>(), B, S_max, Hq,
-                     Hkv, (float)scale, cur_stream());
+  if (B > 0)
+    attn_decode_launch(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
+                       O.data_ptr(), kv_lens.data_ptr<int>(),
+                       slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq,
+                       Hkv, (float)scale, cur_stream());
   return O;
 }
 
@@ -368,38 +465,69 @@ torch::Tensor attn_decode_qkv(torch::Tensor qkv, torch::Tensor Kc,
                               torch::Tensor slot_ids, int64_t Hq,
                               int64_t Hkv, double scale) {
   // fused rope + cache-write + decode attention (attention_decode.hip)
-  CHECK_GPU(qkv); CHECK_CONTIG(qkv); CHECK_BF16(qkv);
-  TORCH_CHECK(positions.scalar_type() == at::kInt);
-  TORCH_CHECK(kv_lens.scalar_type() == at::kInt);
-  TORCH_CHECK(slot_ids.scalar_type() == at::kInt);
-  const int B = (int)qkv.size(0);
+  const char* op = "attn_decode_qkv";
+  check_packed_qkv(op, qkv, Hq, Hkv);
+  const int64_t B = qkv.size(0);
+  check_kv_cache(op, Kc, Vc, Hq, Hkv, qkv);
   const int S_max = (int)Kc.size(1);
-  const int D = (int)Kc.size(3);
-  TORCH_CHECK(D == 128, "attn_decode_qkv: head_dim must be 128");
-  TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D,
-              "attn_decode_qkv: qkv width mismatch");
-  auto O = torch::empty({B, Hq, (long)D}, qkv.options());
-  attn_decode_qkv_launch(qkv.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
-                         O.data_ptr(), cos_tab.data_ptr(),
-                         sin_tab.data_ptr(), positions.data_ptr<int>(),
-                         kv_lens.data_ptr<int>(),
-                         slot_ids.data_ptr<int>(), B, S_max, (int)Hq,
-                         (int)Hkv, (float)scale, cur_stream());
+  check_rope_tables(op, cos_tab, sin_tab, S_max, qkv);
+  check_index(op, "positions", positions, B, qkv);
+  check_index(op, "kv_lens", kv_lens, B, qkv);
+  check_index(op, "slot_ids", slot_ids, B, qkv);
+  check_grid(op, B, Hq);
+  auto O = torch::empty({B, Hq, (int64_t)ATT_D}, qkv.options());
+  if (B > 0)
+    attn_decode_qkv_launch(qkv.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
+                           O.data_ptr(), cos_tab.data_ptr(),
+                           sin_tab.data_ptr(), positions.data_ptr<int>(),
+                           kv_lens.data_ptr<int>(),
+                           slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq,
+                           (int)Hkv, (float)scale, cur_stream());
   return O;
+}
+
+// W8 [O, I] e4m3fn bytes with one fp32 scale per output row.
+static void check_fp8_weight(const char* op, const torch::Tensor& W8,
+                             const torch::Tensor& scale, int64_t I,
+                             const torch::Tensor& first) {
+  TORCH_CHECK(W8.defined() && (W8.scalar_type() == at::kByte ||
+                               W8.scalar_type() == at::kFloat8_e4m3fn),
+              op, ": W8 must be uint8 or float8_e4m3fn, got ",
+              W8.scalar_type());
+  check_dense(op, "W8", W8, W8.scalar_type(), first);
+  TORCH_CHECK(W8.dim() == 2 && W8.size(1) == I, op,
+              ": W8 must be [O, I] with I = ", I, ", got ", W8.sizes());
+  TORCH_CHECK(W8.size(0) >= 1 &&
+                  W8.size(0) <= std::numeric_limits<int>::max(),
+              op, ": W8 must have at least one row, got ", W8.sizes());
+  check_dense(op, "scale", scale, at::kFloat, first);
+  TORCH_CHECK(scale.numel() == W8.size(0), op, ": scale must have O = ",
+              W8.size(0), " elements, got ", scale.numel());
 }
 
 std::vector<torch::Tensor> skinny_gemm_fp8_norm(
     torch::Tensor x, torch::Tensor res, torch::Tensor nw, double eps,
     torch::Tensor W8, torch::Tensor scale, bool want_xout) {
   // norm-fused fp8 GEMV (skinny_gemm.hip): y = rmsnorm(x+res)*nw @ W8^T
-  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
+  const char* op = "skinny_gemm_fp8_norm";
+  check_dense(op, "x", x, at::kBFloat16, x);
+  TORCH_CHECK(x.dim() == 2, op, ": x must be [N, I], got ", x.sizes());
   const int N = (int)x.size(0), I = (int)x.size(1);
+  TORCH_CHECK(I >= 1024 && I <= 4096 && I % 1024 == 0, op,
+              ": I must be 1024, 2048, 3072 or 4096, got ", I);
+  TORCH_CHECK(N >= 1 && N <= 2, op, ": N must be 1 or 2, got ", N);
+  check_fp8_weight(op, W8, scale, I, x);
   const int O = (int)W8.size(0);
-  TORCH_CHECK(I <= 4096 && I % 1024 == 0,
-              "fp8_norm: I must be <= 4096 and 1024-aligned");
-  TORCH_CHECK(N >= 1 && N <= 2, "fp8_norm: N <= 2");
-  TORCH_CHECK(O % 2 == 0, "fp8_norm: O must be even");
+  TORCH_CHECK(O % 2 == 0, op, ": O must be even, got ", O);
+  check_dense(op, "nw", nw, at::kBFloat16, x);
+  TORCH_CHECK(nw.numel() == I, op, ": nw must have I = ", I,
+              " elements, got ", nw.numel());
   const bool has_res = res.defined() && res.numel() > 0;
+  if (has_res) {
+    check_dense(op, "res", res, at::kBFloat16, x);
+    TORCH_CHECK(res.sizes() == x.sizes(), op, ": res must be empty or have "
+                "x's shape ", x.sizes(), ", got ", res.sizes());
+  }
   auto y = torch::empty({N, O}, x.options());
   torch::Tensor xout;
   if (want_xout) xout = torch::empty_like(x);
@@ -481,21 +609,19 @@ torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x) {
 torch::Tensor skinny_gemm_fp8(torch::Tensor X, torch::Tensor W8,
                               torch::Tensor scale) {
   // Y[N,O] = X[N,I] @ (scale[o] * W8[O,I])^T ; W8 = OCP e4m3fn bytes.
-  CHECK_GPU(X); CHECK_CONTIG(X); CHECK_BF16(X);
-  CHECK_GPU(W8); CHECK_CONTIG(W8);
-  TORCH_CHECK(W8.scalar_type() == at::kByte ||
-              W8.scalar_type() == at::kFloat8_e4m3fn,
-              "W8 must be uint8/float8_e4m3fn");
-  CHECK_GPU(scale); CHECK_CONTIG(scale);
-  TORCH_CHECK(scale.scalar_type() == at::kFloat, "scale must be fp32");
-  int N = X.size(0), I = X.size(1), O = W8.size(0);
-  TORCH_CHECK(W8.size(1) == I, "skinny_gemm_fp8: inner dims mismatch");
-  TORCH_CHECK(scale.numel() == O, "skinny_gemm_fp8: scale size");
-  TORCH_CHECK(N >= 1 && N <= 8, "skinny_gemm_fp8: N must be 1..8");
-  TORCH_CHECK(I % 16 == 0, "skinny_gemm_fp8: I must be 16-aligned");
+  const char* op = "skinny_gemm_fp8";
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(N >= 1 && N <= 8, op, ": N must be 1..8, got ", N);
+  TORCH_CHECK(I >= 16 && I % 16 == 0 &&
+                  I <= std::numeric_limits<int>::max(),
+              op, ": I must be a positive multiple of 16, got ", I);
+  check_fp8_weight(op, W8, scale, I, X);
+  const int64_t O = W8.size(0);
   auto y = torch::empty({N, O}, X.options());
   skinny_gemm_fp8_launch(W8.data_ptr(), scale.data_ptr<float>(),
-                         X.data_ptr(), y.data_ptr(), N, I, O,
+                         X.data_ptr(), y.data_ptr(), (int)N, (int)I, (int)O,
                          cur_stream());
   return y;
 }
@@ -517,38 +643,60 @@ torch::Tensor skinny_gemm(torch::Tensor X, torch::Tensor W) {
 std::vector<torch::Tensor> rmsnorm_res(torch::Tensor x, torch::Tensor res,
                                        torch::Tensor w, double eps) {
   // (x + res, rmsnorm(x + res) * w) in one kernel (decode_fused.hip)
-  CHECK_GPU(x); CHECK_CONTIG(x); CHECK_BF16(x);
-  CHECK_GPU(res); CHECK_CONTIG(res); CHECK_BF16(res);
-  const int H = (int)x.size(-1);
-  long long rows = x.numel() / H;
-  TORCH_CHECK(res.sizes() == x.sizes(), "rmsnorm_res: shape mismatch");
-  TORCH_CHECK(H % 256 == 0 && H <= 8192, "rmsnorm_res: H must be a "
-              "multiple of 256 and <= 8192");
+  const char* op = "rmsnorm_res";
+  check_dense(op, "x", x, at::kBFloat16, x);
+  TORCH_CHECK(x.dim() >= 1, op, ": x must be [..., H], got a scalar");
+  const int64_t H = x.size(-1);
+  TORCH_CHECK(H >= 256 && H % 256 == 0 && H <= 8192, op,
+              ": H must be a multiple of 256 and <= 8192, got ", H);
+  check_dense(op, "res", res, at::kBFloat16, x);
+  TORCH_CHECK(res.sizes() == x.sizes(), op, ": res must have x's shape ",
+              x.sizes(), ", got ", res.sizes());
+  check_dense(op, "w", w, at::kBFloat16, x);
+  TORCH_CHECK(w.numel() == H, op, ": w must have H = ", H,
+              " elements, got ", w.numel());
+  const int64_t rows = x.numel() / H;
+  TORCH_CHECK(rows <= std::numeric_limits<int>::max(), op, ": ", rows,
+              " rows exceed the grid limit 2^31 - 1");
   auto x_out = torch::empty_like(x);
   auto h_out = torch::empty_like(x);
-  rmsnorm_res_launch(x.data_ptr(), res.data_ptr(), w.data_ptr(),
-                     x_out.data_ptr(), h_out.data_ptr(), (int)rows, H,
-                     (float)eps, cur_stream());
+  if (rows > 0)
+    rmsnorm_res_launch(x.data_ptr(), res.data_ptr(), w.data_ptr(),
+                       x_out.data_ptr(), h_out.data_ptr(), (int)rows, (int)H,
+                       (float)eps, cur_stream());
   return {x_out, h_out};
 }
 
 void decode_advance(torch::Tensor logits, torch::Tensor stage,
                     torch::Tensor ring, torch::Tensor ctr) {
   // fused greedy argmax + in-graph decode state bump (decode_fused.hip)
-  CHECK_GPU(logits); CHECK_CONTIG(logits); CHECK_BF16(logits);
-  CHECK_GPU(stage); CHECK_CONTIG(stage);
-  CHECK_GPU(ring); CHECK_CONTIG(ring);
-  TORCH_CHECK(stage.dtype() == torch::kInt32, "decode_advance: stage int32");
-  TORCH_CHECK(ring.dtype() == torch::kInt64, "decode_advance: ring int64");
-  TORCH_CHECK(ctr.dtype() == torch::kInt64, "decode_advance: ctr int64");
-  const long long V = logits.size(-1);
-  const long long b = logits.numel() / V;
-  TORCH_CHECK(stage.size(0) == 6 && stage.size(1) == b,
-              "decode_advance: stage must be [6, b]");
-  TORCH_CHECK(ring.size(1) == b, "decode_advance: ring must be [chunk, b]");
-  decode_advance_launch(logits.data_ptr(), V, stage.data_ptr(), b,
-                        ring.data_ptr(), ctr.data_ptr(),
-                        (int)ring.size(0), cur_stream());
+  const char* op = "decode_advance";
+  check_dense(op, "logits", logits, at::kBFloat16, logits);
+  TORCH_CHECK(logits.dim() >= 1, op,
+              ": logits must be [b, V], got a scalar");
+  const int64_t V = logits.size(-1);
+  TORCH_CHECK(V >= 1 && V <= std::numeric_limits<int>::max(), op,
+              ": V must be in [1, 2^31 - 1], got ", V);
+  const int64_t b = logits.numel() / V;
+  check_dense(op, "stage", stage, at::kInt, logits);
+  TORCH_CHECK(stage.dim() == 2 && stage.size(0) == 6 && stage.size(1) == b,
+              op, ": stage must be [6, b] = [6, ", b, "], got ",
+              stage.sizes());
+  check_dense(op, "ring", ring, at::kLong, logits);
+  TORCH_CHECK(ring.dim() == 2 && ring.size(0) >= 1 &&
+                  ring.size(0) <= std::numeric_limits<int>::max() &&
+                  ring.size(1) == b,
+              op, ": ring must be [chunk >= 1, b] = [chunk, ", b, "], got ",
+              ring.sizes());
+  check_dense(op, "ctr", ctr, at::kLong, logits);
+  TORCH_CHECK(ctr.numel() == 1, op, ": ctr must hold one element, got ",
+              ctr.sizes());
+  TORCH_CHECK(b <= std::numeric_limits<int>::max(), op, ": b = ", b,
+              " rows exceed the grid limit 2^31 - 1");
+  if (b > 0)
+    decode_advance_launch(logits.data_ptr(), V, stage.data_ptr(), b,
+                          ring.data_ptr(), ctr.data_ptr(),
+                          (int)ring.size(0), cur_stream());
 }
 
 // ---- seeded decode sampling (decode_sample.hip) ---------------------------
@@ -623,18 +771,25 @@ torch::Tensor rope_kvwrite(torch::Tensor qkv, torch::Tensor kc,
                            torch::Tensor slot_ids, int64_t Hq,
                            int64_t Hkv) {
   // packed-qkv rope + KV-cache scatter (decode_fused.hip)
-  CHECK_GPU(qkv); CHECK_CONTIG(qkv); CHECK_BF16(qkv);
-  const int D = (int)kc.size(3), S_max = (int)kc.size(1);
-  const int n = (int)qkv.size(0);
-  TORCH_CHECK(D == 128, "rope_kvwrite: head_dim must be 128");
-  TORCH_CHECK(qkv.size(1) == (Hq + 2 * Hkv) * D,
-              "rope_kvwrite: packed width mismatch");
-  auto q = torch::empty({n, (long)Hq, (long)D}, qkv.options());
-  rope_kvwrite_launch(qkv.data_ptr(), q.data_ptr(), kc.data_ptr(),
-                      vc.data_ptr(), cos_tab.data_ptr(),
-                      sin_tab.data_ptr(), positions.data_ptr(),
-                      slot_ids.data_ptr(), n, (int)Hq, (int)Hkv, D, S_max,
-                      cur_stream());
+  const char* op = "rope_kvwrite";
+  check_packed_qkv(op, qkv, Hq, Hkv);
+  const int64_t n = qkv.size(0);
+  check_kv_cache(op, kc, vc, Hq, Hkv, qkv);
+  const int S_max = (int)kc.size(1);
+  check_rope_tables(op, cos_tab, sin_tab, S_max, qkv);
+  check_index(op, "positions", positions, n, qkv);
+  check_index(op, "slot_ids", slot_ids, n, qkv);
+  // 16 lanes per (token, head) row, 256 per block
+  TORCH_CHECK(n * (Hq + 2 * Hkv) <= std::numeric_limits<int>::max(), op,
+              ": n * (Hq + 2 * Hkv) = ", n * (Hq + 2 * Hkv),
+              " exceeds the grid limit 2^31 - 1");
+  auto q = torch::empty({n, Hq, (int64_t)ATT_D}, qkv.options());
+  if (n > 0)
+    rope_kvwrite_launch(qkv.data_ptr(), q.data_ptr(), kc.data_ptr(),
+                        vc.data_ptr(), cos_tab.data_ptr(),
+                        sin_tab.data_ptr(), positions.data_ptr(),
+                        slot_ids.data_ptr(), (int)n, (int)Hq, (int)Hkv,
+                        ATT_D, S_max, cur_stream());
   return q;
 }
 

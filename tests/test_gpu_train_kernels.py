@@ -28,73 +28,16 @@ import math
 import pytest
 import torch
 
+from _fp64_check import (TINY, U16, U32, bf16_values, check, f32, rejects,
+                         tol_bf16, tol_f32, within)
 from skypilot_amd import ops
 from skypilot_amd.train.optim import FusedAdamW
 
 gpu = pytest.mark.gpu
 
-U16 = 2.0 ** -8    # bf16 unit roundoff
-U32 = 2.0 ** -24   # fp32 unit roundoff
-TINY = 1e-30
-
 
 def dev():
     return torch.device("cuda:0")
-
-
-def f32(v):
-    """A Python float as the kernel receives it: rounded to fp32."""
-    return torch.tensor(v, dtype=torch.float32).double().item()
-
-
-# ===========================================================================
-# The checker.
-# ===========================================================================
-def tol_bf16(ref, A, K=1, roundings=1):
-    return roundings * 2 * U16 * ref.abs() + 4 * K * U32 * A + TINY
-
-
-def tol_f32(A, K=1):
-    return 4 * K * U32 * A + TINY
-
-
-def within(got, ref, tol):
-    """(ok, worst err/tol, flat index of the worst element)."""
-    got = got.detach().cpu().double()
-    assert got.shape == ref.shape, (got.shape, ref.shape)
-    ratio = (got - ref).abs() / tol
-    ratio = torch.where(torch.isfinite(ratio), ratio,
-                        torch.full_like(ratio, float("inf")))
-    if ratio.numel() == 0:
-        return True, 0.0, -1
-    worst = int(ratio.argmax())
-    r = float(ratio.reshape(-1)[worst])
-    return r <= 1.0, r, worst
-
-
-def check(name, got, ref, tol):
-    ok, r, worst = within(got, ref, tol)
-    print(f"[fp64] {name}: worst err/tol = {r:.3g}")
-    if not ok:
-        g = got.detach().cpu().double().reshape(-1)
-        bad = int(((g - ref.reshape(-1)).abs() > tol.reshape(-1)).sum()
-                  + (~torch.isfinite(g)).sum())
-        idx, rest = [], worst
-        for n in reversed(ref.shape):
-            rest, i = divmod(rest, n)
-            idx.insert(0, i)
-        idx = tuple(idx)
-        raise AssertionError(
-            f"{name}: {bad} of {g.numel()} elements out of tolerance; worst "
-            f"at {idx}: got {g[worst].item()!r}, ref "
-            f"{ref.reshape(-1)[worst].item()!r}, tol "
-            f"{tol.reshape(-1)[worst].item():.3g} (err/tol {r:.3g})")
-    return r
-
-
-def bf16_values(t):
-    """Round to bf16 and return as fp32 (what a bf16 kernel input holds)."""
-    return t.bfloat16().float()
 
 
 # ===========================================================================
@@ -715,11 +658,6 @@ def test_adamw_reference_matches_cpu_fallback(bucket_views):
 # ===========================================================================
 # CPU part 2: the checker rejects known-wrong results, one defect each.
 # ===========================================================================
-def rejects(got, ref, tol):
-    ok, _, _ = within(got, ref, tol)
-    return not ok
-
-
 def _collect_failures(log):
     def fn(name, got, ref, tol):
         if rejects(got, ref, tol):
