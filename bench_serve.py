@@ -74,6 +74,9 @@ def main():
                     help="request i of a batch uses seed + i")
     ap.add_argument("--device-sampling", action="store_true",
                     help="sample in the decode graph instead of on the host")
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="KV cache format (fp8: e4m3fn rows with "
+                         "power-of-two row scales)")
     ap.add_argument("--stall-prompts", type=int, default=0,
                     help="after the batches, also measure what a running "
                          "stream sees when this many --prompt-len prompts "
@@ -88,7 +91,10 @@ def main():
                  device="cuda:0" if torch.cuda.is_available() else "cpu",
                  max_seq=4096, max_batch=args.max_batch,
                  prefill_chunk=args.prefill_chunk,
-                 device_sampling=args.device_sampling)
+                 device_sampling=args.device_sampling,
+                 kv_dtype=args.kv_dtype)
+    print(f"kv_dtype={args.kv_dtype} max_batch={eng.max_batch} "
+          f"kv_cache_bytes={eng.cache.bytes_needed(eng.cfg, eng.cache.max_batch, eng.max_seq, args.kv_dtype)}")
     if args.fp8:
         print(f"fp8 decode weights: {eng.enable_fp8_decode()} tensors")
     eng.start()

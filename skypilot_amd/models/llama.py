@@ -82,6 +82,30 @@ def rope_tables(cfg: LlamaConfig, device, dtype=torch.float32):
     return freqs.cos().to(dtype).contiguous(), freqs.sin().to(dtype).contiguous()
 
 
+def prefill_cache_write(attn, k, v, infer_ctx):
+    """Whole-prompt prefill: store the (unpadded) K/V rows of each
+    sequence of the batch for decode.  With an fp8 cache this is one
+    quantising write per layer; the prefill's own attention still runs on
+    the unquantised K/V.  Shared by Attention and TPAttention."""
+    slots = (infer_ctx.prefill_slots
+             if infer_ctx.prefill_slots is not None
+             else [infer_ctx.prefill_slot])
+    lens = (infer_ctx.prefill_lens
+            if infer_ctx.prefill_lens is not None
+            else [infer_ctx.prefill_len])
+    cache = infer_ctx.cache
+    if cache.kv_dtype == "fp8":
+        if infer_ctx.kv_write_idx is None:  # built once per forward
+            def i32(vals):
+                return torch.tensor(vals, dtype=torch.int32, device=k.device)
+            infer_ctx.kv_write_idx = (i32(slots), i32([0] * len(slots)),
+                                      i32(lens))
+        cache.write_rows_fp8(attn.layer_idx, k, v, *infer_ctx.kv_write_idx)
+        return
+    for i, (slot, ln) in enumerate(zip(slots, lens)):
+        cache.write_prefill(attn.layer_idx, slot, k[i:i + 1], v[i:i + 1], ln)
+
+
 def append_attention(attn, q, k, v, infer_ctx):
     """Chunked prefill (infer_ctx.mode == "append"): row i of sequence b
     is the token at position append_start[b] + i.  The chunk's valid K/V
@@ -89,6 +113,17 @@ def append_attention(attn, q, k, v, infer_ctx):
     only, so the chunk sees the rows earlier chunks left there.  Shared
     by Attention and the tensor-parallel TPAttention."""
     cache = infer_ctx.cache
+    if cache.kv_dtype == "fp8":
+        # one quantising write for the whole batch, then the fp8 kernel;
+        # the chunk attends its own rows as the cache holds them
+        li = attn.layer_idx
+        cache.write_rows_fp8(li, k, v, infer_ctx.append_slots,
+                             infer_ctx.append_start, infer_ctx.append_lens)
+        return ops.attn_append_fp8(q, cache.k[li], cache.v[li],
+                                   cache.k_exp[li], cache.v_exp[li],
+                                   infer_ctx.append_slots,
+                                   infer_ctx.append_start,
+                                   infer_ctx.append_lens, attn.scale)
     for i, (slot, start, ln) in enumerate(zip(infer_ctx.append_slots_l,
                                               infer_ctx.append_start_l,
                                               infer_ctx.append_lens_l)):
@@ -150,10 +185,17 @@ class Attention(nn.Module):
             # of rope_kvwrite + attn_decode (the current token's k/v is
             # attended from registers; the cache row is written for
             # future steps by one block per kv head).
-            o = ops.attn_decode_qkv(
-                qkv, cache.k[self.layer_idx], cache.v[self.layer_idx],
-                cos, sin, positions, infer_ctx.kv_lens,
-                infer_ctx.slot_ids_i32, self.n_q, self.n_kv, self.scale)
+            li = self.layer_idx
+            if cache.kv_dtype == "fp8":
+                o = ops.attn_decode_qkv_fp8(
+                    qkv, cache.k[li], cache.v[li], cache.k_exp[li],
+                    cache.v_exp[li], cos, sin, positions, infer_ctx.kv_lens,
+                    infer_ctx.slot_ids_i32, self.n_q, self.n_kv, self.scale)
+            else:
+                o = ops.attn_decode_qkv(
+                    qkv, cache.k[li], cache.v[li], cos, sin, positions,
+                    infer_ctx.kv_lens, infer_ctx.slot_ids_i32, self.n_q,
+                    self.n_kv, self.scale)
             return ops.decode_linear(o.reshape(B, self.n_q * d),
                                      self.wo.weight).view(B, S, -1)
         lin = torch.nn.functional.linear
@@ -171,15 +213,7 @@ class Attention(nn.Module):
         else:  # prefill: plain causal attention over the prompt; the
             # (unpadded) K/V rows land in the cache for decode.  Rows of
             # a batched prefill are independent sequences.
-            slots = (infer_ctx.prefill_slots
-                     if infer_ctx.prefill_slots is not None
-                     else [infer_ctx.prefill_slot])
-            lens = (infer_ctx.prefill_lens
-                    if infer_ctx.prefill_lens is not None
-                    else [infer_ctx.prefill_len])
-            for i, (slot, ln) in enumerate(zip(slots, lens)):
-                infer_ctx.cache.write_prefill(self.layer_idx, slot,
-                                              k[i:i + 1], v[i:i + 1], ln)
+            prefill_cache_write(self, k, v, infer_ctx)
             o = ops.attention(q, k, v, self.scale, causal=True)
         return lin(o.reshape(B, S, self.n_q * d), self.wo.weight)
 

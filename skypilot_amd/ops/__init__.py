@@ -379,6 +379,130 @@ def attn_append(q, kc, vc, slot_ids, q_start, q_lens, scale):
     return attn_append_ref(q, kc, vc, slot_ids, q_start, q_lens, scale)
 
 
+# ---- FP8 KV cache (docs/KERNELS.md "FP8 KV cache") ------------------------
+# A row is the 128 values of one (token, kv head), K or V: 128 OCP e4m3fn
+# codes plus one E8M0 exponent byte e, scale 2^(e-127).  The two functions
+# below are the definition, in plain torch with integer bit arithmetic;
+# the kernels (kv_fp8.h) reproduce them bit for bit.
+def kv_quantize(x: torch.Tensor):
+    """x [..., D] -> (codes uint8 [..., D], exp uint8 [...]).  With
+    amax = max |x_i| in fp32, n is the smallest integer with
+    amax <= 448 * 2^n, clamped to [-126, 127] (0 for amax == 0); exp =
+    n + 127 and code_i = e4m3fn(x_i * 2^-n), round to nearest even.  Both
+    scalings are by a power of two and exact.  Rows holding NaN or Inf
+    give unspecified contents."""
+    xf = x.detach().float()
+    amax = xf.abs().amax(-1)
+    u = amax.contiguous().view(torch.int32) & 0x7FFFFFFF
+    # 448 = 1.75 * 2^8, and 0x600000 is the fp32 mantissa of 1.75
+    n = (u >> 23) - 135 + ((u & 0x7FFFFF) > 0x600000).to(torch.int32)
+    n = n.clamp(-126, 127)
+    n = torch.where(u == 0, torch.zeros_like(n), n)
+    # 2^-n from its fp32 bits (n <= 121 for a finite amax)
+    inv = ((127 - n).clamp(min=1) << 23).view(torch.float32)
+    codes = (xf * inv.unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes.contiguous(), (n + 127).to(torch.uint8)
+
+
+def kv_dequantize(codes: torch.Tensor, exp: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [..., D], exp uint8 [...] -> code * 2^(exp-127) as
+    fp32 (every such value is exactly representable in bf16)."""
+    scale = (exp.to(torch.int32) << 23).view(torch.float32)
+    return codes.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)
+
+
+def kv_write_fp8(k, v, kc, vc, ke, ve, slot_ids, starts, lens):
+    """Quantise rows of k, v [n, S, Hkv, 128] bf16 into the FP8 cache
+    (kc, vc uint8 [slots, S_max, Hkv, 128]; ke, ve uint8 [slots, S_max,
+    Hkv]): row i < lens[b] of sequence b goes to [slot_ids[b],
+    starts[b] + i].  Rows at or past lens[b] or S_max are skipped, and so
+    is a sequence whose slot is outside [0, slots) or whose start is
+    negative.  slot_ids / starts / lens are int32 [n] on k's device; the
+    GPU path (kv_write_fp8.hip, one launch) never syncs on them."""
+    if k.is_cuda:
+        C = _require_native("kv_write_fp8")
+        C.kv_write_fp8(k.contiguous(), v.contiguous(), kc, vc, ke, ve,
+                       slot_ids, starts, lens)
+        return
+    n, S = k.shape[0], k.shape[1]
+    slots, S_max = kc.shape[0], kc.shape[1]
+    for b in range(n):
+        slot, start, ln = int(slot_ids[b]), int(starts[b]), int(lens[b])
+        if slot < 0 or slot >= slots or start < 0:
+            continue
+        ln = min(ln, S, S_max - start)
+        if ln <= 0:
+            continue
+        kc[slot, start:start + ln], ke[slot, start:start + ln] = \
+            kv_quantize(k[b, :ln])
+        vc[slot, start:start + ln], ve[slot, start:start + ln] = \
+            kv_quantize(v[b, :ln])
+
+
+def _kv_dequant_slots(kc, vc, ke, ve, slot_ids):
+    """Dequantised copies of the slots in use, and their new indices."""
+    idx = torch.as_tensor(slot_ids, device=kc.device).long()
+    ok = (idx >= 0) & (idx < kc.shape[0])
+    idx = torch.where(ok, idx, torch.zeros_like(idx))
+    local = torch.where(ok, torch.arange(idx.numel(), device=kc.device),
+                        torch.full_like(idx, -1))
+    return (kv_dequantize(kc[idx], ke[idx]), kv_dequantize(vc[idx], ve[idx]),
+            local)
+
+
+def attn_decode_fp8(q, kc, vc, ke, ve, kv_lens, slot_ids, scale):
+    """attn_decode over the dequantised rows of an FP8 cache.  CPU only:
+    the GPU model path runs the fused attn_decode_qkv_fp8 and there is no
+    unfused HIP kernel."""
+    if q.is_cuda:
+        raise RuntimeError(
+            "skypilot_amd.ops.attn_decode_fp8 has no HIP kernel; the GPU "
+            "path is attn_decode_qkv_fp8")
+    kd, vd, local = _kv_dequant_slots(kc, vc, ke, ve, slot_ids)
+    return attn_decode_ref(q, kd, vd, kv_lens, local, scale)
+
+
+def attn_decode_qkv_fp8(qkv, kc, vc, ke, ve, cos, sin, positions, kv_lens,
+                        slot_ids, Hq, Hkv, scale):
+    """attn_decode_qkv over the FP8 KV cache (attention_decode_fp8.hip):
+    rope of q and k in fp32, the current k and v quantised and written at
+    (slot, position), attention over the dequantised rows 0..position, the
+    current one included - the output is a function of the cache contents
+    after the call.  CPU: the same composed from kv_quantize, the
+    references and attn_decode_fp8."""
+    D = kc.shape[3]
+    if qkv.is_cuda:
+        C = _require_native("attn_decode_qkv_fp8")
+        return C.attn_decode_qkv_fp8(qkv.contiguous(), kc, vc, ke, ve, cos,
+                                     sin, positions.int(), kv_lens.int(),
+                                     slot_ids.int(), Hq, Hkv, scale)
+    n = qkv.shape[0]
+    q, k, v = qkv.split([Hq * D, Hkv * D, Hkv * D], dim=-1)
+    qr = rope_ref(q.reshape(n, Hq, D).float(), cos, sin, positions.long())
+    kr = rope_ref(k.reshape(n, Hkv, D).float(), cos, sin, positions.long())
+    sl, pos = slot_ids.long(), positions.long()
+    kc[sl, pos], ke[sl, pos] = kv_quantize(kr)
+    vc[sl, pos], ve[sl, pos] = kv_quantize(v.reshape(n, Hkv, D))
+    return attn_decode_fp8(qr, kc, vc, ke, ve, kv_lens, slot_ids,
+                           scale).to(qkv.dtype)
+
+
+def attn_append_fp8(q, kc, vc, ke, ve, slot_ids, q_start, q_lens, scale):
+    """attn_append over the FP8 KV cache (attention_append.hip): on the
+    GPU bit-identical to attn_append on a bf16 cache holding
+    kv_dequantize of the same codes.  The caller writes the chunk's rows
+    first (kv_write_fp8)."""
+    if q.is_cuda:
+        C = _require_native("attn_append_fp8")
+        return C.attn_append_fp8(q.contiguous(), kc, vc, ke, ve, slot_ids,
+                                 q_start, q_lens, scale)
+    kd, vd, local = _kv_dequant_slots(kc, vc, ke, ve, slot_ids)
+    lens = torch.where(local < 0, torch.zeros_like(local),
+                       torch.as_tensor(q_lens).long())
+    return attn_append_ref(q, kd, vd, local.clamp(min=0), q_start, lens,
+                           scale)
+
+
 # ---- fp8 decode weights (serving; VERDICT r01 #7) -------------------------
 # Per-output-row e4m3fn quantization: W_row ~= scale_r * fp8(W_row/scale_r).
 # Registered weights reroute decode_linear through the fp8 GEMV (half the
@@ -736,4 +860,6 @@ __all__ = [
     "native", "native_available", "rmsnorm_ref", "rope_ref",
     "attention_ref", "cross_entropy_ref", "attn_decode_ref",
     "attn_append", "attn_append_ref",
+    "kv_quantize", "kv_dequantize", "kv_write_fp8", "attn_decode_qkv_fp8",
+    "attn_append_fp8", "attn_decode_fp8",
 ]

@@ -28,7 +28,9 @@ HIP_SOURCES = [
     "attention_bwd.hip",
     "attention_bwd_v3.hip",
     "attention_decode.hip",
+    "attention_decode_fp8.hip",
     "attention_append.hip",
+    "kv_write_fp8.hip",
     "swiglu.hip",
     "skinny_gemm.hip",
     "wgrad_gemm.hip",

@@ -26,8 +26,19 @@
 //    only stores zeros and returns; padding rows inside a partly valid
 //    tile get the attention of their position, which is finite.
 //  * No lse output (inference only).
+//
+// The kernel body (attn_append_body.h) is included once per K/V source:
+// the bf16 cache described above, and AppendTileFp8, which reads the FP8
+// KV cache (kv_fp8.h): 8-byte chunks of e4m3fn codes plus the row's
+// exponent byte,
+// with the same clamp to kv_len - 1 for the codes and for the exponent and
+// the same zero V rows; staging converts code * 2^n to bf16, which is
+// exact, before the swz/swzT LDS writes.  From the first barrier on the
+// two instantiations run the same code on the same LDS contents, so
+// attn_append_fp8 equals attn_append on the dequantised cache bit for bit.
 #include "attn_append.h"
 #include "common.h"
+#include "kv_fp8.h"
 
 #define BM 64  // q rows per block
 #define BN 64  // kv rows per tile
@@ -65,208 +76,88 @@ __device__ __forceinline__ void append_load_tile(
   }
 }
 
-extern "C" __global__ __launch_bounds__(256, 2) void attn_append_kernel(
-    const unsigned short* __restrict__ Q, const unsigned short* __restrict__ Kc,
-    const unsigned short* __restrict__ Vc, unsigned short* __restrict__ O,
-    const int* __restrict__ slot_ids, const int* __restrict__ q_start,
-    const int* __restrict__ q_lens, int Sq, int Hq, int Hkv, int slots,
-    int S_max, float scale) {
-  __shared__ unsigned short k_lds[BN * ATT_D];    // [kv][d], swizzled, 16KB
-  __shared__ unsigned short vt_lds[ATT_D * BN];   // [d][kv], swizzled, 16KB
-
-  const int qt = gridDim.x - 1 - blockIdx.x;
-  const int bh = blockIdx.y;
-  const int b = bh / Hq;
-  const int qh = bh % Hq;
-  const int kvh = qh / (Hq / Hkv);
-  const int qbase = qt * BM;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int w = tid >> 6;               // wave id: q rows [16w, 16w+16)
-  const int lrow = lane & 15;           // q column owned by this lane
-  const int lgrp = lane >> 4;
-
-  // Per-sequence scalars (SGPRs).  An index the cache cannot hold (slot
-  // outside [0, slots), negative start) makes the sequence empty instead
-  // of an out-of-bounds read.
-  const int slot = __builtin_amdgcn_readfirstlane(slot_ids[b]);
-  const int qs = __builtin_amdgcn_readfirstlane(q_start[b]);
-  int ql = __builtin_amdgcn_readfirstlane(q_lens[b]);
-  ql = min(max(ql, 0), Sq);
-  if (slot < 0 || slot >= slots || qs < 0) ql = 0;
-  const int kv_len = (int)min((long long)qs + ql, (long long)S_max);
-
-  const long long q_rowstride = (long long)Hq * ATT_D;
-  const long long kv_rowstride = (long long)Hkv * ATT_D;
-  const unsigned short* Qb = Q + ((long long)b * Sq * Hq + qh) * ATT_D;
-  unsigned short* Ob = O + ((long long)b * Sq * Hq + qh) * ATT_D;
-
-  if (qbase >= ql) {
-    // Padding-only tile (every tile of an empty sequence): finite output,
-    // no cache row read.  Thread t zeroes chunk t&15 of rows (t>>4)+16i.
+// The FP8 K/V source of the kernel body: load() fetches one thread's share
+// of a tile into registers (issued one tile ahead), k(i) / v(i) hand the
+// staging loop chunk i as 8 bf16.  Same chunk/row map; a chunk of 8 elements is 8 bytes of codes, and the
+// thread's four chunks lie in two rows ((tid>>3) and (tid>>3)+32), so it
+// carries two exponents per tensor.
+struct AppendTileFp8 {
+  const unsigned char* Kb;
+  const unsigned char* Vb;
+  const unsigned char* Keb;
+  const unsigned char* Veb;
+  long long kv_rowstride;
+  int Hkv;
+  i32x2 kpre[4], vpre[4];
+  unsigned ke[2], ve[2];  // exponent bytes of rows (tid>>3), (tid>>3)+32
+  __device__ __forceinline__ AppendTileFp8(const unsigned char* Kc,
+                                           const unsigned char* Vc,
+                                           const unsigned char* Ke,
+                                           const unsigned char* Ve,
+                                           long long row0,
+                                           long long rowstride, int Hkv_)
+      : Kb(Kc + row0 * ATT_D),
+        Vb(Vc + row0 * ATT_D),
+        Keb(Ke + row0),
+        Veb(Ve + row0),
+        kv_rowstride(rowstride), Hkv(Hkv_) {}
+  __device__ __forceinline__ void load(int kvbase, int kv_len, int tid) {
+    if (kvbase + BN <= kv_len) {
+      // Whole tile valid (block-uniform): plain loads, no clamp and no
+      // select, so nothing consumes a register before the staging loop
+      // and the loads stay in flight under the MFMAs.
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = qbase + (tid >> 4) + 16 * i;
-      *(s16x8*)(Ob + (long long)row * q_rowstride + (tid & 15) * 8) =
-          s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
-    return;
-  }
-  // From here ql >= 1, so kv_len >= 1 and kv row 0 is visible to every
-  // row of the tile: no softmax column ends empty.
-
-  const unsigned short* Kb =
-      Kc + ((long long)slot * S_max * Hkv + kvh) * ATT_D;
-  const unsigned short* Vb =
-      Vc + ((long long)slot * S_max * Hkv + kvh) * ATT_D;
-
-  // Q as B-fragments: B[k=d][n=q]: lane holds Q[q=lrow][d=ks*32+lgrp*8+j].
-  s16x8 q_b[4];
-  {
-    const int qrow = qbase + 16 * w + lrow;
-    const unsigned short* src = Qb + (long long)qrow * q_rowstride;
+      for (int h = 0; h < 2; ++h) {
+        const long long row = kvbase + ((tid >> 3) | (h << 5));
+        ke[h] = Keb[row * Hkv];
+        ve[h] = Veb[row * Hkv];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      q_b[ks] = *(const s16x8*)(src + ks * 32 + lgrp * 8);
-  }
-
-  // Per-lane softmax state for q column lrow (replicated across lgrp).
-  float m_run = -INFINITY, l_run = 0.f;
-  f32x4 o_t[8];  // O^T: C[row=d=ct*16+lgrp*4+r][col=q=lrow]
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct) o_t[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // kv rows the tile can see: up to the diagonal of its last row, and
-  // never past kv_len.
-  const int kv_end = (int)min((long long)kv_len, (long long)qs + qbase + BM);
-  const int n_kv_tiles = (kv_end + BN - 1) / BN;
-
-  s16x8 kpre[4], vpre[4];
-  append_load_tile(Kb, Vb, kv_rowstride, 0, kv_len, tid, kpre, vpre);
-
-  // Absolute positions, capped at S_max: kv < kv_len <= S_max, so a cap
-  // there changes no comparison and keeps them 32-bit.
-  const int my_q = qbase + 16 * w + lrow;  // row of the chunk
-  const int my_pos = (int)min((long long)qs + my_q, (long long)S_max);
-  const int wave_pos0 =
-      (int)min((long long)qs + qbase + 16 * w, (long long)S_max);
-  for (int kt = 0; kt < n_kv_tiles; ++kt) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int s_ch = (tid & 7) | ((i & 1) << 3);
-      int s_row = (tid >> 3) | ((i >> 1) << 5);
-      *(s16x8*)((char*)k_lds + swz(s_row * 256 + s_ch * 16, s_row)) =
-          kpre[i];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        int d = s_ch * 8 + j;
-        *(unsigned short*)((char*)vt_lds + swzT(d * 128 + s_row * 2, d)) =
-            (unsigned short)vpre[i][j];
-      }
-    }
-    __syncthreads();
-    if (kt + 1 < n_kv_tiles)
-      append_load_tile(Kb, Vb, kv_rowstride, (kt + 1) * BN, kv_len, tid,
-                       kpre, vpre);
-    const int kvbase = kt * BN;
-
-    // ---- S^T = scale * K Q^T : 64 kv rows x 16 q cols for this wave.
-    f32x4 st_acc[4];
-#pragma unroll
-    for (int kv4 = 0; kv4 < 4; ++kv4)
-      st_acc[kv4] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-      for (int kv4 = 0; kv4 < 4; ++kv4) {
-        int krow = kv4 * 16 + lrow;
-        s16x8 a_k = *(const s16x8*)((char*)k_lds +
-            swz(krow * 256 + (ks * 32 + lgrp * 8) * 2, krow));
-        st_acc[kv4] = MFMA_BF16(as_bf16x8(a_k), as_bf16x8(q_b[ks]),
-                                st_acc[kv4]);
-      }
-
-    // ---- mask + in-register column softmax (q = lrow on every lane).
-    // The diagonal is at the absolute position; the tile needs the mask
-    // when it reaches past the wave's first position or past kv_len.
-    const bool need_mask =
-        (kvbase + BN - 1 > wave_pos0) || (kvbase + BN > kv_len);
-    float mx = -INFINITY;
-#pragma unroll
-    for (int kv4 = 0; kv4 < 4; ++kv4)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float s = st_acc[kv4][r] * scale;
-        if (need_mask) {
-          int kv = kvbase + kv4 * 16 + lgrp * 4 + r;
-          if (kv > my_pos || kv >= kv_len) s = -INFINITY;
+        for (int lo = 0; lo < 2; ++lo) {
+          const long long r =
+              row * kv_rowstride + ((tid & 7) | (lo << 3)) * 8;
+          kpre[2 * h + lo] = *(const i32x2*)(Kb + r);
+          vpre[2 * h + lo] = *(const i32x2*)(Vb + r);
         }
-        st_acc[kv4][r] = s;
-        mx = fmaxf(mx, s);
       }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float m_new = fmaxf(m_run, mx);
-    float m_safe = (m_new == -INFINITY) ? 0.f : m_new;
-    float corr = (m_run == -INFINITY) ? 0.f : __expf(m_run - m_safe);
-    m_run = m_new;
-    float rs = 0.f;
+      return;
+    }
 #pragma unroll
-    for (int kv4 = 0; kv4 < 4; ++kv4)
+    for (int h = 0; h < 2; ++h) {
+      const int row = kvbase + ((tid >> 3) | (h << 5));
+      // never past the valid rows, codes and exponent alike
+      const long long row_c = min(row, kv_len - 1);
+      ke[h] = Keb[row_c * Hkv];
+      ve[h] = Veb[row_c * Hkv];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float e = (st_acc[kv4][r] == -INFINITY)
-                      ? 0.f : __expf(st_acc[kv4][r] - m_safe);
-        st_acc[kv4][r] = e;  // P^T stays in the S registers
-        rs += e;
-      }
-    rs += __shfl_xor(rs, 16, 64);
-    rs += __shfl_xor(rs, 32, 64);
-    l_run = l_run * corr + rs;
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o_t[ct][r] *= corr;
-
-    // ---- P^T -> B-fragments via cross-lane shuffles (parent's recipe).
-    s16x8 p_b[2];
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        int src = (2 * (lgrp & 1) + (j >> 2)) * 16 + lrow;
-        float v0 = __shfl(st_acc[2 * ks][j & 3], src, 64);
-        float v1 = __shfl(st_acc[2 * ks + 1][j & 3], src, 64);
-        p_b[ks][j] = (short)f2bf_trunc((lgrp >> 1) ? v1 : v0);
+      for (int lo = 0; lo < 2; ++lo) {
+        const long long r =
+            row_c * kv_rowstride + ((tid & 7) | (lo << 3)) * 8;
+        kpre[2 * h + lo] = *(const i32x2*)(Kb + r);
+        const i32x2 vv = *(const i32x2*)(Vb + r);
+        // code 0 is +0: rows at or past kv_len are staged as zeros
+        vpre[2 * h + lo] = (row < kv_len) ? vv : i32x2{0, 0};
       }
     }
-
-    // ---- O^T += V^T P^T : A from vt_lds.
-#pragma unroll
-    for (int ct = 0; ct < 8; ++ct)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        int vrow = ct * 16 + lrow;
-        s16x8 a_vt = *(const s16x8*)((char*)vt_lds +
-            swzT(vrow * 128 + (ks * 32 + lgrp * 8) * 2, vrow));
-        o_t[ct] = MFMA_BF16(as_bf16x8(a_vt), as_bf16x8(p_b[ks]), o_t[ct]);
-      }
   }
-
-  // ---- epilogue: O[q][d] = O^T[d][q] / l (s16x4 stores, d block
-  // ct*16 + lgrp*4).
-  const float inv_l = (l_run > 0.f) ? 1.f / l_run : 0.f;
-  unsigned short* orow = Ob + (long long)my_q * q_rowstride;
-#pragma unroll
-  for (int ct = 0; ct < 8; ++ct) {
-    s16x4 ov;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ov[r] = (short)f2bf(o_t[ct][r] * inv_l);
-    *(s16x4*)(orow + ct * 16 + lgrp * 4) = ov;
+  __device__ __forceinline__ s16x8 k(int i) const {
+    return kv8_dequant_bf16(kpre[i], kv8_scale(ke[i >> 1]));
   }
-}
+  __device__ __forceinline__ s16x8 v(int i) const {
+    return kv8_dequant_bf16(vpre[i], kv8_scale(ve[i >> 1]));
+  }
+};
+
+#define APPEND_KERNEL attn_append_kernel
+#define APPEND_FP8 0
+#include "attn_append_body.h"
+#undef APPEND_KERNEL
+#undef APPEND_FP8
+
+#define APPEND_KERNEL attn_append_fp8_kernel
+#define APPEND_FP8 1
+#include "attn_append_body.h"
+#undef APPEND_KERNEL
+#undef APPEND_FP8
 
 extern "C" void attn_append_launch(const void* Q, const void* Kc,
                                    const void* Vc, void* O,
@@ -278,5 +169,21 @@ extern "C" void attn_append_launch(const void* Q, const void* Kc,
   hipLaunchKernelGGL(attn_append_kernel, grid, dim3(256), 0, stream,
                      (const unsigned short*)Q, (const unsigned short*)Kc,
                      (const unsigned short*)Vc, (unsigned short*)O, slot_ids,
+                     q_start, q_lens, Sq, Hq, Hkv, slots, S_max, scale);
+}
+
+extern "C" void attn_append_fp8_launch(const void* Q, const void* Kc,
+                                       const void* Vc, const void* Ke,
+                                       const void* Ve, void* O,
+                                       const int* slot_ids,
+                                       const int* q_start, const int* q_lens,
+                                       int n, int Sq, int Hq, int Hkv,
+                                       int slots, int S_max, float scale,
+                                       hipStream_t stream) {
+  dim3 grid(Sq / BM, n * Hq);
+  hipLaunchKernelGGL(attn_append_fp8_kernel, grid, dim3(256), 0, stream,
+                     (const unsigned short*)Q, (const unsigned char*)Kc,
+                     (const unsigned char*)Vc, (const unsigned char*)Ke,
+                     (const unsigned char*)Ve, (unsigned short*)O, slot_ids,
                      q_start, q_lens, Sq, Hq, Hkv, slots, S_max, scale);
 }

@@ -13,6 +13,7 @@
 
 #include "attn_append.h"
 #include "attn_launch.h"
+#include "kv_fp8_launch.h"
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -486,6 +487,144 @@ torch::Tensor attn_decode_qkv(torch::Tensor qkv, torch::Tensor Kc,
   return O;
 }
 
+// ---- FP8 KV cache (kv_fp8.h) ------------------------------------------------
+// Code tensors uint8 [slots, S_max, Hkv, 128] and exponent tensors uint8
+// [slots, S_max, Hkv], all four dense and of one cache.
+static void check_kv_cache_fp8(const char* op, const torch::Tensor& Kc,
+                               const torch::Tensor& Vc,
+                               const torch::Tensor& Ke,
+                               const torch::Tensor& Ve, int64_t Hq,
+                               int64_t Hkv, const torch::Tensor& first) {
+  const torch::Tensor* cs[] = {&Kc, &Vc};
+  const char* cnames[] = {"Kc", "Vc"};
+  for (int i = 0; i < 2; ++i) {
+    check_dense(op, cnames[i], *cs[i], at::kByte, first);
+    TORCH_CHECK(cs[i]->dim() == 4, op, ": ", cnames[i],
+                " must be [slots, S_max, Hkv, 128], got ", cs[i]->dim(),
+                " dims");
+    TORCH_CHECK(cs[i]->size(3) == ATT_D, op, ": ", cnames[i],
+                " head dim must be 128, got ", cs[i]->size(3));
+  }
+  TORCH_CHECK(Vc.sizes() == Kc.sizes(), op, ": Vc must have Kc's shape ",
+              Kc.sizes(), ", got ", Vc.sizes());
+  TORCH_CHECK(Kc.size(0) > 0 && Kc.size(1) > 0 &&
+                  Kc.size(0) <= std::numeric_limits<int>::max() &&
+                  Kc.size(1) <= std::numeric_limits<int>::max(),
+              op, ": Kc must hold at least one slot and one row, got ",
+              Kc.sizes());
+  const torch::Tensor* es[] = {&Ke, &Ve};
+  const char* enames[] = {"Ke", "Ve"};
+  for (int i = 0; i < 2; ++i) {
+    check_dense(op, enames[i], *es[i], at::kByte, first);
+    TORCH_CHECK(es[i]->dim() == 3 && es[i]->size(0) == Kc.size(0) &&
+                    es[i]->size(1) == Kc.size(1) &&
+                    es[i]->size(2) == Kc.size(2),
+                op, ": ", enames[i], " must be [slots, S_max, Hkv] = [",
+                Kc.size(0), ", ", Kc.size(1), ", ", Kc.size(2), "], got ",
+                es[i]->sizes());
+  }
+  TORCH_CHECK(Hkv > 0 && Hkv == Kc.size(2), op, ": Hkv = ", Hkv,
+              " must equal Kc.size(2) = ", Kc.size(2));
+  TORCH_CHECK(Hq > 0 && Hq % Hkv == 0, op, ": Hq = ", Hq,
+              " must be a positive multiple of Hkv = ", Hkv);
+}
+
+// Quantising cache write of prefill / append rows (kv_write_fp8.hip):
+// row i < lens[b] of k, v [n, S, Hkv, 128] goes to
+// [slot_ids[b], starts[b] + i].
+void kv_write_fp8(torch::Tensor k, torch::Tensor v, torch::Tensor Kc,
+                  torch::Tensor Vc, torch::Tensor Ke, torch::Tensor Ve,
+                  torch::Tensor slot_ids, torch::Tensor starts,
+                  torch::Tensor lens) {
+  const char* op = "kv_write_fp8";
+  const torch::Tensor* ts[] = {&k, &v};
+  const char* names[] = {"k", "v"};
+  for (int i = 0; i < 2; ++i) {
+    check_dense(op, names[i], *ts[i], at::kBFloat16, k);
+    TORCH_CHECK(ts[i]->dim() == 4 && ts[i]->size(3) == ATT_D, op, ": ",
+                names[i], " must be [n, S, Hkv, 128], got ", ts[i]->sizes());
+  }
+  TORCH_CHECK(v.sizes() == k.sizes(), op, ": v must have k's shape ",
+              k.sizes(), ", got ", v.sizes());
+  const int64_t n = k.size(0), S = k.size(1), Hkv = k.size(2);
+  check_kv_cache_fp8(op, Kc, Vc, Ke, Ve, Hkv, Hkv, k);
+  check_index(op, "slot_ids", slot_ids, n, k);
+  check_index(op, "starts", starts, n, k);
+  check_index(op, "lens", lens, n, k);
+  TORCH_CHECK(S <= std::numeric_limits<int>::max() &&
+                  n * S * Hkv <= std::numeric_limits<int>::max(),
+              op, ": n * S * Hkv = ", n * S * Hkv,
+              " exceeds the grid limit 2^31 - 1");
+  if (n * S * Hkv > 0)
+    kv_write_fp8_launch(k.data_ptr(), v.data_ptr(), Kc.data_ptr(),
+                        Vc.data_ptr(), Ke.data_ptr(), Ve.data_ptr(),
+                        slot_ids.data_ptr<int>(), starts.data_ptr<int>(),
+                        lens.data_ptr<int>(), (int)n, (int)S, (int)Hkv,
+                        (int)Kc.size(0), (int)Kc.size(1), cur_stream());
+}
+
+// attn_append over the FP8 KV cache (attention_append.hip).
+torch::Tensor attn_append_fp8(torch::Tensor Q, torch::Tensor Kc,
+                              torch::Tensor Vc, torch::Tensor Ke,
+                              torch::Tensor Ve, torch::Tensor slot_ids,
+                              torch::Tensor q_start, torch::Tensor q_lens,
+                              double scale) {
+  const char* op = "attn_append_fp8";
+  check_dense(op, "Q", Q, at::kBFloat16, Q);
+  TORCH_CHECK(Q.dim() == 4 && Q.size(3) == ATT_D, op,
+              ": Q must be [n, Sq, Hq, 128], got ", Q.sizes());
+  const int64_t n = Q.size(0), Sq = Q.size(1), Hq = Q.size(2);
+  TORCH_CHECK(Sq > 0 && Sq % 64 == 0, op,
+              ": chunk length Sq must be a positive multiple of 64, got ",
+              Sq);
+  check_kv_cache_fp8(op, Kc, Vc, Ke, Ve, Hq, Kc.dim() == 4 ? Kc.size(2) : 0,
+                     Q);
+  TORCH_CHECK(n > 0 && n * Hq <= 65535, op, ": n * Hq = ", n * Hq,
+              " must be in [1, 65535] (one grid row per sequence and head)");
+  check_index(op, "slot_ids", slot_ids, n, Q);
+  check_index(op, "q_start", q_start, n, Q);
+  check_index(op, "q_lens", q_lens, n, Q);
+  auto O = torch::empty_like(Q);
+  attn_append_fp8_launch(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(),
+                         Ke.data_ptr(), Ve.data_ptr(), O.data_ptr(),
+                         slot_ids.data_ptr<int>(), q_start.data_ptr<int>(),
+                         q_lens.data_ptr<int>(), (int)n, (int)Sq, (int)Hq,
+                         (int)Kc.size(2), (int)Kc.size(0), (int)Kc.size(1),
+                         (float)scale, cur_stream());
+  return O;
+}
+
+// Fused rope + cache write + decode attention over the FP8 KV cache
+// (attention_decode_fp8.hip); the contract of attn_decode_qkv.
+torch::Tensor attn_decode_qkv_fp8(torch::Tensor qkv, torch::Tensor Kc,
+                                  torch::Tensor Vc, torch::Tensor Ke,
+                                  torch::Tensor Ve, torch::Tensor cos_tab,
+                                  torch::Tensor sin_tab,
+                                  torch::Tensor positions,
+                                  torch::Tensor kv_lens,
+                                  torch::Tensor slot_ids, int64_t Hq,
+                                  int64_t Hkv, double scale) {
+  const char* op = "attn_decode_qkv_fp8";
+  check_packed_qkv(op, qkv, Hq, Hkv);
+  const int64_t B = qkv.size(0);
+  check_kv_cache_fp8(op, Kc, Vc, Ke, Ve, Hq, Hkv, qkv);
+  const int S_max = (int)Kc.size(1);
+  check_rope_tables(op, cos_tab, sin_tab, S_max, qkv);
+  check_index(op, "positions", positions, B, qkv);
+  check_index(op, "kv_lens", kv_lens, B, qkv);
+  check_index(op, "slot_ids", slot_ids, B, qkv);
+  check_grid(op, B, Hq);
+  auto O = torch::empty({B, Hq, (int64_t)ATT_D}, qkv.options());
+  if (B > 0)
+    attn_decode_qkv_fp8_launch(
+        qkv.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ke.data_ptr(),
+        Ve.data_ptr(), O.data_ptr(), cos_tab.data_ptr(), sin_tab.data_ptr(),
+        positions.data_ptr<int>(), kv_lens.data_ptr<int>(),
+        slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq, (int)Hkv,
+        (float)scale, cur_stream());
+  return O;
+}
+
 // W8 [O, I] e4m3fn bytes with one fp32 scale per output row.
 static void check_fp8_weight(const char* op, const torch::Tensor& W8,
                              const torch::Tensor& scale, int64_t I,
@@ -883,6 +1022,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_tokens", &sample_tokens);
   m.def("decode_sample_advance", &decode_sample_advance);
   m.def("attn_decode_qkv", &attn_decode_qkv);
+  m.def("kv_write_fp8", &kv_write_fp8);
+  m.def("attn_decode_qkv_fp8", &attn_decode_qkv_fp8);
+  m.def("attn_append_fp8", &attn_append_fp8);
   m.def("skinny_gemm_fp8_norm", &skinny_gemm_fp8_norm);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

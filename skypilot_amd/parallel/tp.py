@@ -99,18 +99,13 @@ class TPAttention(nn.Module):
             o = ops.attention(q, k, v, self.scale, causal=True)
         elif infer_ctx.mode == "prefill":
             # batched prefill (same contract as models/llama.py:117)
-            slots = (infer_ctx.prefill_slots
-                     if infer_ctx.prefill_slots is not None
-                     else [infer_ctx.prefill_slot])
-            lens = (infer_ctx.prefill_lens
-                    if infer_ctx.prefill_lens is not None
-                    else [infer_ctx.prefill_len])
-            for i, (slot, ln) in enumerate(zip(slots, lens)):
-                infer_ctx.cache.write_prefill(self.layer_idx, slot,
-                                              k[i:i + 1], v[i:i + 1], ln)
+            L.prefill_cache_write(self, k, v, infer_ctx)
             o = ops.attention(q, k, v, self.scale, causal=True)
         elif infer_ctx.mode == "append":
             o = L.append_attention(self, q, k, v, infer_ctx)
+        elif infer_ctx.cache.kv_dtype == "fp8":
+            o = self._decode_fp8(q, k, v, infer_ctx).view(
+                B, 1, self.n_q, d)
         else:
             infer_ctx.cache.write_decode(self.layer_idx, infer_ctx.slots,
                                          infer_ctx.pos, k, v)
@@ -120,6 +115,33 @@ class TPAttention(nn.Module):
                 infer_ctx.slot_ids_i32, self.scale).view(B, 1, self.n_q, d)
         out = self.wo(o.reshape(B, S, self.n_q * d))
         return _AllReduceFwd.apply(out, self.group)
+
+
+    def _decode_fp8(self, q, k, v, infer_ctx):
+        """Decode step over an fp8 cache.  q and k arrive roped (the split
+        projections above), so the fused kernel runs with an identity rope
+        row per sequence: it quantises k and v, writes them and attends
+        the dequantised rows, the current one included.  On the CPU the
+        same comes from write_decode + attn_decode_fp8."""
+        cache, li = infer_ctx.cache, self.layer_idx
+        B, d = q.shape[0], self.cfg.head_dim
+        if not q.is_cuda:
+            cache.write_decode(li, infer_ctx.slots, infer_ctx.pos, k, v)
+            return ops.attn_decode_fp8(
+                q.view(B, self.n_q, d), cache.k[li], cache.v[li],
+                cache.k_exp[li], cache.v_exp[li], infer_ctx.kv_lens,
+                infer_ctx.slot_ids_i32, self.scale)
+        ident = getattr(self, "_rope_ident", None)
+        if ident is None or ident[0].shape[0] < cache.max_seq:
+            ident = (torch.ones(cache.max_seq, d // 2, device=q.device),
+                     torch.zeros(cache.max_seq, d // 2, device=q.device))
+            self._rope_ident = ident
+        qkv = torch.cat([q.reshape(B, -1), k.reshape(B, -1),
+                         v.reshape(B, -1)], -1)
+        return ops.attn_decode_qkv_fp8(
+            qkv, cache.k[li], cache.v[li], cache.k_exp[li], cache.v_exp[li],
+            ident[0], ident[1], infer_ctx.pos.int(), infer_ctx.kv_lens,
+            infer_ctx.slot_ids_i32, self.n_q, self.n_kv, self.scale)
 
 
 class TPMLP(nn.Module):

@@ -36,7 +36,7 @@ import torch.distributed as dist
 
 from skypilot_amd import ops
 from skypilot_amd.models.llama import build_model
-from skypilot_amd.serve.kv_cache import KVCache
+from skypilot_amd.serve.kv_cache import KV_DTYPES, KVCache
 
 
 @dataclass
@@ -64,6 +64,9 @@ class InferenceContext:
     append_slots_l: Optional[list] = None
     append_start_l: Optional[list] = None
     append_lens_l: Optional[list] = None
+    # fp8 cache, whole-prompt prefill: (slots, starts, lens) int32 device
+    # tensors of the batch's cache write, built by the first layer
+    kv_write_idx: Optional[tuple] = None
 
 
 @dataclass
@@ -103,7 +106,15 @@ class Engine:
                  use_graphs: bool = True, model=None, tp_group=None,
                  tp_rank: int = 0, tp_world: int = 1,
                  prefill_chunk: Optional[int] = None,
-                 device_sampling: bool = False):
+                 device_sampling: bool = False,
+                 kv_dtype: str = "bf16"):
+        # "fp8" stores the KV cache as e4m3fn rows with power-of-two row
+        # scales (docs/KERNELS.md "FP8 KV cache"): 129 instead of 256
+        # bytes per (token, kv head) row.
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(
+                f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
         # Chunked prefill: None keeps whole-prompt prefills (_prefill).
         # The append kernel tiles the chunk by 64 rows.
         if prefill_chunk is not None and (
@@ -150,13 +161,13 @@ class Engine:
                     hbm_budget_gb = 0.5
             self.cache = KVCache.sized_for_memory(
                 self.cfg, self.max_seq, int(hbm_budget_gb * 1e9),
-                self.device)
+                self.device, kv_dtype=kv_dtype)
         else:
             # +1 slot when graphs are on: the graph-padding scratch slot
             # must not cost a unit of serving concurrency.
             extra = 1 if (use_graphs and self.device.type == "cuda") else 0
             self.cache = KVCache(self.cfg, max_batch + extra, self.max_seq,
-                                 self.device)
+                                 self.device, kv_dtype=kv_dtype)
         self.max_batch = self.cache.max_batch
         self.free_slots = list(range(self.max_batch))
         self.active: Dict[int, Request] = {}  # slot -> request

@@ -173,7 +173,7 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
     return app
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--port", type=int,
@@ -197,7 +197,16 @@ def main():
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree; run under torchrun "
                          "with one rank per GPU (70B serving: --tp 8)")
-    args = ap.parse_args()
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="KV cache format: fp8 stores e4m3fn rows with "
+                         "power-of-two row scales (about half the cache "
+                         "bytes: twice the slots or context, half the "
+                         "decode-attention traffic)")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     if args.tp > 1:
         # TP serving (BASELINE config 5's serve twin): every rank builds
         # its shard; rank 0 leads (scheduler + HTTP), others follow the
@@ -221,7 +230,8 @@ def main():
                         max_batch=args.max_batch, model=shard,
                         tp_rank=rank, tp_world=args.tp,
                         prefill_chunk=args.prefill_chunk,
-                        device_sampling=args.device_sampling)
+                        device_sampling=args.device_sampling,
+                        kv_dtype=args.kv_dtype)
         if args.fp8_decode:
             engine.enable_fp8_decode()
         if rank > 0:
@@ -238,7 +248,8 @@ def main():
     engine = Engine(args.model, device=args.device, max_seq=args.max_seq,
                     max_batch=args.max_batch,
                     prefill_chunk=args.prefill_chunk,
-                    device_sampling=args.device_sampling)
+                    device_sampling=args.device_sampling,
+                    kv_dtype=args.kv_dtype)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode()
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
