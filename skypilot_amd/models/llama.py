@@ -6,7 +6,9 @@ CDNA4 kernels in :mod:`skypilot_amd.ops`:
 * tensors stay in ``[B, S, H, D]`` layout end-to-end — the attention
   kernels read strided rows directly, so there are no head transposes;
 * RMSNorm / RoPE / attention / cross-entropy are the fused HIP kernels;
-* GEMMs are plain ``nn.Linear`` (hipBLASLt on ROCm);
+* GEMMs are hipBLASLt through ``F.linear``; in training the block
+  projections go through ``ops.linear`` / ``ops.qkv_linear``, whose
+  backward picks the weight gradient's operand layout per shape;
 * RoPE cos/sin tables are precomputed fp32 buffers (on-device trig would
   make the op VALU-bound — guide Appendix B).
 
@@ -198,10 +200,14 @@ class Attention(nn.Module):
                     self.n_kv, self.scale)
             return ops.decode_linear(o.reshape(B, self.n_q * d),
                                      self.wo.weight).view(B, S, -1)
-        lin = torch.nn.functional.linear
-        q = lin(x, self.wq.weight, self.wq.bias).view(B, S, self.n_q, d)
-        k = lin(x, self.wk.weight, self.wk.bias).view(B, S, self.n_kv, d)
-        v = lin(x, self.wv.weight, self.wv.bias).view(B, S, self.n_kv, d)
+        # F.linear forwards; the backward's weight gradients go through
+        # the extension's linear_wgrad (one packed product for q, k and v)
+        q, k, v = ops.qkv_linear(x, self.wq.weight, self.wk.weight,
+                                 self.wv.weight, self.wq.bias, self.wk.bias,
+                                 self.wv.bias)
+        q = q.view(B, S, self.n_q, d)
+        k = k.view(B, S, self.n_kv, d)
+        v = v.view(B, S, self.n_kv, d)
         q = ops.rope(q.reshape(B * S, self.n_q, d), cos, sin,
                      positions).view(B, S, self.n_q, d)
         k = ops.rope(k.reshape(B * S, self.n_kv, d), cos, sin,
@@ -215,7 +221,7 @@ class Attention(nn.Module):
             # a batched prefill are independent sequences.
             prefill_cache_write(self, k, v, infer_ctx)
             o = ops.attention(q, k, v, self.scale, causal=True)
-        return lin(o.reshape(B, S, self.n_q * d), self.wo.weight)
+        return ops.linear(o.reshape(B, S, self.n_q * d), self.wo.weight)
 
 
 class MLP(nn.Module):
@@ -228,7 +234,7 @@ class MLP(nn.Module):
 
     def forward(self, x, infer_ctx=None):
         decode = infer_ctx is not None and infer_ctx.mode == "decode"
-        lin = ops.decode_linear if decode else torch.nn.functional.linear
+        lin = ops.decode_linear if decode else ops.linear
         return lin(ops.swiglu(lin(x, self.w_gate_up.weight)),
                    self.w_down.weight)
 

@@ -308,6 +308,94 @@ def swiglu(gu):
     return _SwiGLUFn.apply(gu)
 
 
+# ---- linear layers of the training path -----------------------------------
+# The forward and the input gradient are the library calls autograd would
+# make.  The weight gradient dW = dy^T x has neither operand contiguous
+# along its contraction (the tokens), the layout the library GEMM is
+# slowest in, so it goes through the extension's linear_wgrad, which may
+# transpose operands first (docs/KERNELS.md "Weight gradients").  `route`:
+# -1 the measured per-shape table, 0 the library call as it was, 1 both
+# operands transposed, 2 dy only.
+def _rows(t):
+    return t.reshape(-1, t.shape[-1])
+
+
+class _LinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, b, route):
+        ctx.save_for_backward(x, w)
+        ctx.route = route
+        return torch.nn.functional.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy2 = _rows(dy)
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = (dy2 @ w).view(x.shape)
+        if ctx.needs_input_grad[1]:
+            dw = native().linear_wgrad(dy2.contiguous(),
+                                       _rows(x).contiguous(), ctx.route)
+        if ctx.needs_input_grad[2]:
+            db = dy2.sum(0)
+        return dx, dw, db, None
+
+
+def linear(x, w, b=None, route: int = -1):
+    """F.linear(x, w, b) whose bf16 GPU backward takes the weight
+    gradient through linear_wgrad.  Forward values are F.linear's own."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16
+            and w.dtype == torch.bfloat16):
+        return torch.nn.functional.linear(x, w, b)
+    _require_native("linear")
+    return _LinearFn.apply(x, w, b, route)
+
+
+class _QKVLinearFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, wq, wk, wv, bq, bk, bv, route):
+        ctx.save_for_backward(x, wq, wk, wv)
+        ctx.route = route
+        lin = torch.nn.functional.linear
+        return lin(x, wq, bq), lin(x, wk, bk), lin(x, wv, bv)
+
+    @staticmethod
+    def backward(ctx, dq, dk, dv):
+        x, wq, wk, wv = ctx.saved_tensors
+        outs = [wq.shape[0], wk.shape[0], wv.shape[0]]
+        # dq|dk|dv side by side: dx and the weight gradient are then one
+        # GEMM each over the packed width, summed in fp32 and rounded once
+        dy = torch.cat([_rows(dq), _rows(dk), _rows(dv)], dim=1)
+        need = ctx.needs_input_grad
+        dx = None
+        if need[0]:
+            dx = (dy @ torch.cat([wq, wk, wv], dim=0)).view(x.shape)
+        dws = [None, None, None]
+        if need[1] or need[2] or need[3]:
+            dws = native().linear_wgrad(dy, _rows(x).contiguous(),
+                                        ctx.route).split(outs, dim=0)
+        dbs = [None, None, None]
+        if need[4] or need[5] or need[6]:
+            dbs = [d if need[4 + i] else None
+                   for i, d in enumerate(dy.sum(0).split(outs))]
+        return (dx, *dws, *dbs, None)
+
+
+def qkv_linear(x, wq, wk, wv, bq=None, bk=None, bv=None, route: int = -1):
+    """The q, k and v projections of one input as one autograd node:
+    (F.linear(x, wq, bq), F.linear(x, wk, bk), F.linear(x, wv, bv)).  The
+    bf16 GPU backward packs dq|dk|dv once and forms dx and the three
+    weight gradients as one GEMM each (no elementwise adds, one bf16
+    rounding per element)."""
+    lin = torch.nn.functional.linear
+    if not (x.is_cuda and x.dtype == torch.bfloat16
+            and wq.dtype == torch.bfloat16):
+        return lin(x, wq, bq), lin(x, wk, bk), lin(x, wv, bv)
+    _require_native("qkv_linear")
+    return _QKVLinearFn.apply(x, wq, wk, wv, bq, bk, bv, route)
+
+
 def attn_decode_ref(q, kc, vc, kv_lens, slot_ids, scale):
     """q: [B, Hq, D]; kc/vc: [slots, S_max, Hkv, D]."""
     B, Hq, D = q.shape
@@ -855,7 +943,8 @@ def rope_kvwrite(qkv, kc, vc, cos, sin, positions, slot_ids, Hq, Hkv):
 
 __all__ = [
     "rmsnorm", "rope", "attention", "fused_cross_entropy", "attn_decode",
-    "swiglu", "decode_linear", "rmsnorm_res", "rope_kvwrite",
+    "swiglu", "linear", "qkv_linear",
+    "decode_linear", "rmsnorm_res", "rope_kvwrite",
     "decode_swiglu_down",
     "native", "native_available", "rmsnorm_ref", "rope_ref",
     "attention_ref", "cross_entropy_ref", "attn_decode_ref",

@@ -709,13 +709,57 @@ torch::Tensor skinny_gemm_swiglu(torch::Tensor GU, torch::Tensor W) {
 }
 
 // Transpose-then-NT weight-gradient GEMM (wgrad_gemm.hip).
+// The kernel moves whole 64x64 tiles of a 2-D tensor, takes int dims and
+// reads and writes 16-byte vectors.
+static bool tile_dims(const torch::Tensor& X) {
+  return X.size(0) > 0 && X.size(1) > 0 && X.size(0) % 64 == 0 &&
+         X.size(1) % 64 == 0 &&
+         X.size(0) <= std::numeric_limits<int>::max() &&
+         X.size(1) <= std::numeric_limits<int>::max();
+}
+static bool aligned16(const torch::Tensor& X) {
+  return reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0;
+}
+static bool transposable(const torch::Tensor& X) {
+  return tile_dims(X) && aligned16(X);
+}
+
+static void check_transpose_arg(const char* op, const char* name,
+                                const torch::Tensor& X,
+                                const torch::Tensor& first) {
+  check_dense(op, name, X, at::kBFloat16, first);
+  TORCH_CHECK(X.dim() == 2, op, ": ", name, " must be 2-D, got ", X.sizes());
+  TORCH_CHECK(aligned16(X), op, ": ", name, " must start on a 16-byte "
+              "boundary (storage offset ", X.storage_offset(), ")");
+}
+
+static void check_transpose_src(const char* op, const char* name,
+                                const torch::Tensor& X,
+                                const torch::Tensor& first) {
+  check_transpose_arg(op, name, X, first);
+  TORCH_CHECK(tile_dims(X), op, ": ", name, " dims must be positive "
+              "multiples of 64 (dims % 64), got ", X.sizes());
+}
+
 torch::Tensor transpose_bf16(torch::Tensor X) {
-  CHECK_GPU(X); CHECK_CONTIG(X); CHECK_BF16(X);
+  check_transpose_src("transpose_bf16", "X", X, X);
   int R = X.size(0), C = X.size(1);
-  TORCH_CHECK(R % 64 == 0 && C % 64 == 0, "transpose_bf16: dims % 64");
   auto Y = torch::empty({C, R}, X.options());
   transpose_bf16_launch(X.data_ptr(), Y.data_ptr(), R, C, cur_stream());
   return Y;
+}
+
+// Y[c, r] = X[r, c] into a caller's contiguous [C, R] tensor, which may
+// be a row range of a larger buffer.
+void transpose_bf16_out(torch::Tensor X, torch::Tensor Y) {
+  const char* op = "transpose_bf16_out";
+  check_transpose_src(op, "X", X, X);
+  check_transpose_arg(op, "Y", Y, X);
+  TORCH_CHECK(Y.size(0) == X.size(1) &&
+              Y.size(1) == X.size(0), op, ": Y must be [", X.size(1), ", ",
+              X.size(0), "] for X ", X.sizes(), ", got ", Y.sizes());
+  transpose_bf16_launch(X.data_ptr(), Y.data_ptr(), (int)X.size(0),
+                        (int)X.size(1), cur_stream());
 }
 
 torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B) {
@@ -743,6 +787,95 @@ torch::Tensor wgrad_tn(torch::Tensor dy, torch::Tensor x) {
   auto dyT = transpose_bf16(dy);
   auto xT = transpose_bf16(x);
   return gemm_nt(dyT, xT);
+}
+
+// ---- Weight gradient of a linear layer ------------------------------------
+// dW [out, in] = dy^T x, dy [M, out], x [M, in], by the library GEMM in
+// one of three operand layouts (docs/KERNELS.md "Weight gradients"):
+//   0  at::mm(dy.t(), x)      the call autograd makes: neither operand is
+//                             contiguous along the contraction M
+//   1  at::linear(dyT, xT)    both transposed first: the forward's layout
+//   2  at::mm(dyT, x)         dy transposed only: the dgrad layout
+// Transposed copies are scratch from the caching allocator, freed on
+// return.  kWgradRoutes holds the layout measured fastest, transposes
+// included, per (sum of outs, in) on MI355X at M = 24,576 (bench_wgrad_
+// layouts.py; docs/BENCHMARKS.md "Weight-gradient layouts"; ms per call,
+// GEMM + transposes).  The same entries also win at M = 8,192, the other
+// token count measured (docs/KERNELS.md), so the table applies from
+// kWgradMinTokens = 8,192 up; nothing below was measured.  Everything not
+// listed, and every shape the transpose kernel cannot take, is 0.
+struct WgradRoute {
+  int64_t out, in;
+  int route;
+};
+static const WgradRoute kWgradRoutes[] = {
+    // gate|up: library 4.782, route 1 4.451, route 2 4.653
+    {28672, 4096, 1},
+    // down: library 2.910, route 1 2.961, route 2 2.668
+    {4096, 14336, 2},
+    // o (4096 x 4096) stays on the library: 0.671 against 0.727 and 0.666
+    // q|k|v (6144 x 4096), which ops.qkv_linear hands over already packed,
+    // stays on the library: 1.045 against 1.077 and 1.061 (as the three
+    // separate products autograd made it was 1.391)
+};
+static const int64_t kWgradMinTokens = 8192;
+
+static int wgrad_table_route(int64_t M, int64_t out, int64_t in) {
+  if (M < kWgradMinTokens) return 0;
+  for (const auto& r : kWgradRoutes)
+    if (r.out == out && r.in == in) return r.route;
+  return 0;
+}
+
+// Several dy that share one x (dq, dk, dv): one [sum out, M] transposed
+// buffer, one GEMM, row views of one [sum out, in] result.
+std::vector<torch::Tensor> linear_wgrad_packed(std::vector<torch::Tensor> dys,
+                                               torch::Tensor x,
+                                               int64_t route) {
+  const char* op = "linear_wgrad";
+  TORCH_CHECK(route >= -1 && route <= 2, op, ": route must be -1 (table), "
+              "0 (library), 1 (both transposed) or 2 (dy transposed), got ",
+              route);
+  TORCH_CHECK(!dys.empty(), op, ": needs at least one dy");
+  check_dense(op, "x", x, at::kBFloat16, x);
+  TORCH_CHECK(x.dim() == 2, op, ": x must be [M, in], got ", x.sizes());
+  const int64_t M = x.size(0), in = x.size(1);
+  int64_t total = 0;
+  // One rule for both routes: route 2 never transposes x, but a shape
+  // with any dim off the 64-tile was not measured on any route, so it
+  // takes the library call as well.
+  bool tiles = transposable(x);
+  for (const auto& dy : dys) {
+    check_dense(op, "dy", dy, at::kBFloat16, x);
+    TORCH_CHECK(dy.dim() == 2 && dy.size(0) == M, op, ": dy must be [M = ",
+                M, ", out], got ", dy.sizes());
+    total += dy.size(1);
+    tiles = tiles && transposable(dy);
+  }
+  if (route < 0) route = wgrad_table_route(M, total, in);
+  std::vector<torch::Tensor> dWs;
+  if (route == 0 || !tiles) {
+    for (const auto& dy : dys) dWs.push_back(at::mm(dy.t(), x));
+    return dWs;
+  }
+  auto dyT = at::empty({total, M}, x.options());
+  int64_t off = 0;
+  for (const auto& dy : dys) {
+    transpose_bf16_out(dy, dyT.narrow(0, off, dy.size(1)));
+    off += dy.size(1);
+  }
+  auto dW = route == 1 ? at::linear(dyT, transpose_bf16(x)) : at::mm(dyT, x);
+  if (dys.size() == 1) return {dW};
+  off = 0;
+  for (const auto& dy : dys) {
+    dWs.push_back(dW.narrow(0, off, dy.size(1)));
+    off += dy.size(1);
+  }
+  return dWs;
+}
+
+torch::Tensor linear_wgrad(torch::Tensor dy, torch::Tensor x, int64_t route) {
+  return linear_wgrad_packed({dy}, x, route)[0];
 }
 
 torch::Tensor skinny_gemm_fp8(torch::Tensor X, torch::Tensor W8,
@@ -1014,6 +1147,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_bf16", &transpose_bf16);
   m.def("gemm_nt", &gemm_nt);
   m.def("wgrad_tn", &wgrad_tn);
+  m.def("transpose_bf16_out", &transpose_bf16_out);
+  m.def("linear_wgrad", &linear_wgrad, py::arg("dy"), py::arg("x"),
+        py::arg("route") = -1);
+  m.def("linear_wgrad_packed", &linear_wgrad_packed, py::arg("dys"),
+        py::arg("x"), py::arg("route") = -1);
   m.def("adamw_step_mt", &adamw_step_mt);
   m.def("skinny_gemm_swiglu", &skinny_gemm_swiglu);
   m.def("rmsnorm_res", &rmsnorm_res);

@@ -11,6 +11,11 @@
 // waits, global_load_lds staging with pre-swizzled sources, XOR LDS
 // swizzle, setprio around MFMA clusters).
 //
+// The training path does not use the hand GEMM (it lost to the library):
+// linear_wgrad in bindings.cpp runs the library's GEMM on operands
+// transposed by transpose_bf16_kernel (docs/KERNELS.md "Weight
+// gradients").
+//
 // No reference counterpart (SkyPilot ships no kernels).
 #include <cstdlib>
 
@@ -21,40 +26,58 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
   __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0)
 
 // ---------------------------------------------------------------------------
-// Tiled bf16 transpose: out[c][r] = in[r][c].  64x64 tiles through
-// padded LDS; vectorized s16x8 on both sides of the staging.
+// Tiled bf16 transpose: out[c][r] = in[r][c].  One wave per 64x64 tile,
+// every memory instruction 16 bytes per lane:
+//   * lane (g, s) = (lane >> 3, lane & 7) loads the 8x8 block at rows
+//     8g.., columns 8s.. as eight 16-byte row pieces; the eight lanes of
+//     one g read one whole 128-byte line per load;
+//   * the 8x8 block is transposed in registers (32 v_perm_b32: each
+//     output dword pairs the same 16-bit half of two rows' dwords);
+//   * the transposed block goes to LDS as eight 16-byte rows of the
+//     [out row][64] image, and comes back with the roles of g and s
+//     swapped, so that the eight lanes of one g again write one whole
+//     128-byte line of `out` per store.
+// LDS rows are 128 bytes, so the 16-byte chunk index is XORed with
+// (out row >> 3): a write's 8-lane groups (s = 0..7 at one g) and a
+// read's 16-lane groups each cover every bank once.  No scalar LDS
+// access, no bank conflict; 8 KB of LDS per wave.
 // ---------------------------------------------------------------------------
-#define TP 72  // padded LDS row (elements)
-extern "C" __global__ __launch_bounds__(256) void transpose_bf16_kernel(
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+extern "C" __global__ __launch_bounds__(64) void transpose_bf16_kernel(
     const unsigned short* __restrict__ in, unsigned short* __restrict__ out,
     int R, int C) {
-  __shared__ unsigned short t[64 * TP];
+  __shared__ u32x4 t[64 * 8];  // [out row][chunk ^ (out row >> 3)]
   const int tiles_r = R >> 6;
   const int tiles_c = C >> 6;
-  const int tid = threadIdx.x;
+  const int g = threadIdx.x >> 3;
+  const int s = threadIdx.x & 7;
   for (long long tile = blockIdx.x; tile < (long long)tiles_r * tiles_c;
        tile += gridDim.x) {
     const int tr = (int)(tile / tiles_c);
     const int tc = (int)(tile % tiles_c);
     const long long r0 = (long long)tr << 6;
     const long long c0 = (long long)tc << 6;
-    __syncthreads();
+    u32x4 v[8];
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int r = (tid >> 3) + 32 * i;
-      int c8 = (tid & 7) * 8;
-      *(s16x8*)&t[r * TP + c8] =
-          *(const s16x8*)(in + (r0 + r) * C + c0 + c8);
+    for (int j = 0; j < 8; ++j)
+      v[j] = *(const u32x4*)(in + (r0 + 8 * g + j) * C + c0 + 8 * s);
+    __syncthreads();  // the previous tile's LDS reads are done
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      // out row 8s + i holds in[8g .. 8g+7][8s + i]: chunk g of that row
+      const unsigned sel = (i & 1) ? 0x07060302u : 0x05040100u;
+      u32x4 o;
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+        o[m] = __builtin_amdgcn_perm(v[2 * m + 1][i >> 1], v[2 * m][i >> 1],
+                                     sel);
+      t[(8 * s + i) * 8 + (g ^ s)] = o;
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      int c = (tid >> 3) + 32 * i;
-      int r8 = (tid & 7) * 8;
-      s16x8 v;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = t[(r8 + j) * TP + c];
-      *(s16x8*)(out + (c0 + c) * R + r0 + r8) = v;
+    for (int i = 0; i < 8; ++i) {
+      const int c = g + 8 * i;  // out row of the tile; c >> 3 == i
+      *(u32x4*)(out + (c0 + c) * R + r0 + 8 * s) = t[c * 8 + (s ^ i)];
     }
   }
 }
@@ -213,7 +236,8 @@ extern "C" void transpose_bf16_launch(const void* in, void* out, int R,
                                       int C, hipStream_t stream) {
   long long tiles = ((long long)R >> 6) * (C >> 6);
   int grid = tiles > 4096 ? 4096 : (int)tiles;
-  hipLaunchKernelGGL(transpose_bf16_kernel, dim3(grid), dim3(256), 0,
+  // one wave per block; 4096 blocks are 16 waves per CU, all resident
+  hipLaunchKernelGGL(transpose_bf16_kernel, dim3(grid), dim3(64), 0,
                      stream, (const unsigned short*)in,
                      (unsigned short*)out, R, C);
 }
