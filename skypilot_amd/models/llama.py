@@ -325,9 +325,11 @@ class Llama(nn.Module):
             return logits
         for blk in self.blocks:
             x = blk(x, cos, sin, positions, infer_ctx)
-        if infer_ctx is not None and infer_ctx.mode == "append":
+        if (infer_ctx is not None and infer_ctx.mode == "append"
+                and not getattr(infer_ctx, "all_rows", False)):
             # Only the last valid row of each chunk can be sampled from:
             # gather it before the norm and the vocab-sized GEMM.  -> [n,1,V]
+            # (all_rows keeps every row: prompt log-probabilities.)
             last = (infer_ctx.append_lens.long() - 1).clamp(min=0)
             x = x[torch.arange(B, device=x.device), last].unsqueeze(1)
         x = ops.rmsnorm(x, self.final_norm, self.cfg.norm_eps)

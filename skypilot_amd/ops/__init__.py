@@ -894,6 +894,109 @@ def decode_sample_advance(logits, stage, ring, ctr, samp):
     C.decode_sample_advance(logits.contiguous(), stage, ring, ctr, samp)
 
 
+# ---- token log-probabilities (docs/KERNELS.md "Token log-probabilities") ---
+LOGPROB_TOP = 20
+_LOG2E_F32 = float(torch.tensor(1.44269504088896340736, dtype=torch.float32))
+
+
+def _logprob_rowvec(x, n, dtype):
+    if isinstance(x, torch.Tensor):
+        t = x.detach().to(device="cpu").to(dtype).reshape(-1)
+    else:
+        t = torch.tensor(x, dtype=dtype).reshape(-1)
+    if t.numel() == 1:
+        t = t.expand(n)
+    if t.numel() != n:
+        raise ValueError(f"expected one value or {n} per-row values, got "
+                         f"{t.numel()}")
+    return t.contiguous()
+
+
+def token_logprobs_reference(logits, ids, n_top):
+    """fp64 CPU reference of the log-probability definition.  logits
+    [n, V] (taken at their bf16/fp32 value), ids [n] chosen tokens, n_top
+    scalar or [n] -> (lp fp32 [n], top_lp fp32 [n, 20], top_ids int32
+    [n, 20]).
+
+    Per row: m = max l, Z_q = sum floor(exp2((l - m) * log2e) * 2^40) as
+    an integer (log2e the fp32 constant), lse = m + ln(Z_q * 2^-40),
+    lp_j = fp32(l_j - lse).  The top list is the first min(N, V) tokens
+    by (value descending, index ascending), padded with (-1, NaN).  A
+    row with a NaN or an infinite maximum, an id outside [0, V) and a row
+    that is off (n_top < 0) give NaN / -1."""
+    l2 = logits.detach().to("cpu").float().double()
+    l2 = l2.reshape(-1, l2.shape[-1])
+    n, V = l2.shape
+    ids_l = _logprob_rowvec(ids, n, torch.int64).tolist()
+    nt_l = _logprob_rowvec(n_top, n, torch.int64).tolist()
+    lp = torch.full((n,), float("nan"), dtype=torch.float32)
+    top_lp = torch.full((n, LOGPROB_TOP), float("nan"), dtype=torch.float32)
+    top_ids = torch.full((n, LOGPROB_TOP), -1, dtype=torch.int32)
+    for i in range(n):
+        N = min(nt_l[i], LOGPROB_TOP)
+        if N < 0:
+            continue
+        l = l2[i]
+        m = float(l.max())           # NaN if the row holds one
+        if not math.isfinite(m):
+            continue
+        w = torch.floor(torch.exp2((l - m) * _LOG2E_F32) * 2.0 ** 40)
+        zq = int(w.to(torch.int64).sum())
+        lse = m + math.log(float(zq) * 2.0 ** -40)
+        vals = (l - lse).float()
+        if 0 <= ids_l[i] < V:
+            lp[i] = vals[ids_l[i]]
+        k = min(N, V)
+        if k > 0:
+            # stable and descending: equal values keep ascending indices
+            order = torch.sort(l, descending=True, stable=True).indices[:k]
+            top_ids[i, :k] = order.to(torch.int32)
+            top_lp[i, :k] = vals[order]
+    return lp, top_lp, top_ids
+
+
+def token_logprobs(logits, ids, n_top, out=None):
+    """Log-probabilities under each row of `logits` [n, V] at temperature
+    1 with no filter: the value of the chosen token ids[i] and the top
+    n_top[i] (<= 20) tokens (decode_sample.hip on GPU, the fp64 reference
+    on CPU).  `n_top` is a scalar or per-row; -1 turns a row off.
+    Returns (lp fp32 [n], top_lp fp32 [n, 20], top_ids int32 [n, 20]);
+    unused entries are (-1, NaN).  On GPU `out` may give the three result
+    tensors, whose off rows are then left untouched."""
+    if not logits.is_cuda:
+        return token_logprobs_reference(logits, ids, n_top)
+    C = _require_native("token_logprobs")
+    if logits.dtype != torch.bfloat16 or logits.dim() != 2:
+        raise ValueError("token_logprobs: logits must be bf16 [n, V] on GPU")
+    n, dev = logits.shape[0], logits.device
+    if not (isinstance(ids, torch.Tensor) and ids.is_cuda):
+        ids = _logprob_rowvec(ids, n, torch.int64).to(dev)
+    if not (isinstance(n_top, torch.Tensor) and n_top.is_cuda):
+        n_top = _logprob_rowvec(n_top, n, torch.int32).to(dev)
+    if out is None:
+        out = (torch.full((n,), float("nan"), dtype=torch.float32,
+                          device=dev),
+               torch.full((n, LOGPROB_TOP), float("nan"),
+                          dtype=torch.float32, device=dev),
+               torch.full((n, LOGPROB_TOP), -1, dtype=torch.int32,
+                          device=dev))
+    lp, top_lp, top_ids = out
+    C.token_logprobs(logits.contiguous(), ids, n_top, lp, top_lp, top_ids)
+    return lp, top_lp, top_ids
+
+
+def decode_logprobs(logits, stage, n_top, lp_ring, top_lp_ring, top_id_ring,
+                    ctr):
+    """In-graph token_logprobs for the decode step, captured after the
+    advance kernel and before ctr += 1: the chosen token of row i is
+    stage[0, i], the results go to row ctr % chunk of the three rings
+    (decode_sample.hip).  stage is only read.  GPU-only: the decode
+    graph never runs on CPU."""
+    C = _require_native("decode_logprobs")
+    C.decode_logprobs(logits.contiguous(), stage, n_top, lp_ring,
+                      top_lp_ring, top_id_ring, ctr)
+
+
 def decode_swiglu_down(gu, weight):
     """silu(gate)*up followed by the down projection.  MEASURED
     NEGATIVE as a fused GEMV (skinny_gemm_swiglu kept for reference):

@@ -56,6 +56,11 @@ void decode_advance_launch(const void*, long long, void*, long long,
                            void*, const void*, int, hipStream_t);
 void sample_tokens_launch(const void*, int, long long, const void*,
                           const void*, void*, void*, hipStream_t);
+void token_logprobs_launch(const void*, int, long long, const void*,
+                           const void*, void*, void*, void*, hipStream_t);
+void decode_logprobs_launch(const void*, int, const void*, long long,
+                            const void*, void*, void*, void*, const void*,
+                            int, hipStream_t);
 void decode_sample_advance_launch(const void*, int, void*, long long, void*,
                                   const void*, int, const void*,
                                   hipStream_t);
@@ -1037,6 +1042,98 @@ void decode_sample_advance(torch::Tensor logits, torch::Tensor stage,
                                  cur_stream());
 }
 
+// ---- token log-probabilities (decode_sample.hip) --------------------------
+static const int64_t kLogprobTop = 20;
+
+// logits [rows, V] with V in [1, 2^23] (the fixed-point sum's bound, as
+// for the sampler); returns V.
+static int64_t check_logprob_logits(const char* op,
+                                    const torch::Tensor& logits) {
+  check_dense(op, "logits", logits, at::kBFloat16, logits);
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be [n, V], got ",
+              logits.sizes());
+  const int64_t V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= kSampleMaxV, op,
+              ": V must be in [1, 2^23], got ", V);
+  TORCH_CHECK(logits.size(0) <= std::numeric_limits<int>::max(), op, ": ",
+              logits.size(0), " rows exceed the grid limit 2^31 - 1");
+  return V;
+}
+
+// Writes lp [n], top_lp [n, 20] and top_ids [n, 20] in place; rows with
+// n_top < 0 are left as they are.  The values of ids and n_top are not
+// read on the host.
+void token_logprobs(torch::Tensor logits, torch::Tensor ids,
+                    torch::Tensor n_top, torch::Tensor lp,
+                    torch::Tensor top_lp, torch::Tensor top_ids) {
+  const char* op = "token_logprobs";
+  const int64_t V = check_logprob_logits(op, logits);
+  const int64_t n = logits.size(0);
+  check_dense(op, "ids", ids, at::kLong, logits);
+  TORCH_CHECK(ids.dim() == 1 && ids.size(0) == n, op, ": ids must be [n] = [",
+              n, "], got ", ids.sizes());
+  check_index(op, "n_top", n_top, n, logits);
+  check_dense(op, "lp", lp, at::kFloat, logits);
+  TORCH_CHECK(lp.dim() == 1 && lp.size(0) == n, op, ": lp must be [n] = [", n,
+              "], got ", lp.sizes());
+  check_dense(op, "top_lp", top_lp, at::kFloat, logits);
+  check_dense(op, "top_ids", top_ids, at::kInt, logits);
+  TORCH_CHECK(top_lp.dim() == 2 && top_lp.size(0) == n &&
+                  top_lp.size(1) == kLogprobTop,
+              op, ": top_lp must be [n, 20] = [", n, ", 20], got ",
+              top_lp.sizes());
+  TORCH_CHECK(top_ids.dim() == 2 && top_ids.size(0) == n &&
+                  top_ids.size(1) == kLogprobTop,
+              op, ": top_ids must be [n, 20] = [", n, ", 20], got ",
+              top_ids.sizes());
+  if (n > 0)
+    token_logprobs_launch(logits.data_ptr(), (int)V, n, ids.data_ptr(),
+                          n_top.data_ptr(), lp.data_ptr(), top_lp.data_ptr(),
+                          top_ids.data_ptr(), cur_stream());
+}
+
+void decode_logprobs(torch::Tensor logits, torch::Tensor stage,
+                     torch::Tensor n_top, torch::Tensor lp_ring,
+                     torch::Tensor top_lp_ring, torch::Tensor top_id_ring,
+                     torch::Tensor ctr) {
+  // in-graph log-probabilities of the token the advance kernel chose
+  const char* op = "decode_logprobs";
+  const int64_t V = check_logprob_logits(op, logits);
+  const int64_t b = logits.size(0);
+  check_dense(op, "stage", stage, at::kInt, logits);
+  TORCH_CHECK(stage.dim() == 2 && stage.size(0) == 6 && stage.size(1) == b,
+              op, ": stage must be [6, b] = [6, ", b, "], got ",
+              stage.sizes());
+  check_index(op, "n_top", n_top, b, logits);
+  check_dense(op, "lp_ring", lp_ring, at::kFloat, logits);
+  TORCH_CHECK(lp_ring.dim() == 2 && lp_ring.size(0) >= 1 &&
+                  lp_ring.size(0) <= std::numeric_limits<int>::max() &&
+                  lp_ring.size(1) == b,
+              op, ": lp_ring must be [chunk >= 1, b] = [chunk, ", b,
+              "], got ", lp_ring.sizes());
+  const int64_t chunk = lp_ring.size(0);
+  check_dense(op, "top_lp_ring", top_lp_ring, at::kFloat, logits);
+  check_dense(op, "top_id_ring", top_id_ring, at::kInt, logits);
+  TORCH_CHECK(top_lp_ring.dim() == 3 && top_lp_ring.size(0) == chunk &&
+                  top_lp_ring.size(1) == b &&
+                  top_lp_ring.size(2) == kLogprobTop,
+              op, ": top_lp_ring must be [chunk, b, 20] = [", chunk, ", ", b,
+              ", 20], got ", top_lp_ring.sizes());
+  TORCH_CHECK(top_id_ring.dim() == 3 && top_id_ring.size(0) == chunk &&
+                  top_id_ring.size(1) == b &&
+                  top_id_ring.size(2) == kLogprobTop,
+              op, ": top_id_ring must be [chunk, b, 20] = [", chunk, ", ", b,
+              ", 20], got ", top_id_ring.sizes());
+  check_dense(op, "ctr", ctr, at::kLong, logits);
+  TORCH_CHECK(ctr.numel() == 1, op, ": ctr must hold one element, got ",
+              ctr.sizes());
+  if (b > 0)
+    decode_logprobs_launch(logits.data_ptr(), (int)V, stage.data_ptr(), b,
+                           n_top.data_ptr(), lp_ring.data_ptr(),
+                           top_lp_ring.data_ptr(), top_id_ring.data_ptr(),
+                           ctr.data_ptr(), (int)chunk, cur_stream());
+}
+
 torch::Tensor rope_kvwrite(torch::Tensor qkv, torch::Tensor kc,
                            torch::Tensor vc, torch::Tensor cos_tab,
                            torch::Tensor sin_tab, torch::Tensor positions,
@@ -1159,6 +1256,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_advance", &decode_advance);
   m.def("sample_tokens", &sample_tokens);
   m.def("decode_sample_advance", &decode_sample_advance);
+  m.def("token_logprobs", &token_logprobs);
+  m.def("decode_logprobs", &decode_logprobs);
   m.def("attn_decode_qkv", &attn_decode_qkv);
   m.def("kv_write_fp8", &kv_write_fp8);
   m.def("attn_decode_qkv_fp8", &attn_decode_qkv_fp8);

@@ -474,3 +474,327 @@ extern "C" void decode_sample_advance_launch(const void* logits, int V,
                      (long long*)ring, (const long long*)ctr, chunk,
                      (const int*)samp);
 }
+
+// ---- token log-probabilities (docs/KERNELS.md "Token log-probabilities") --
+// log-softmax of one row at temperature 1 with no filter: the value of
+// one chosen token and the first N tokens in the total order (value
+// descending, index ascending), N <= LOGPROB_TOP.  The row is read with
+// the sampler's row_pass; Z is the sampler's fixed-point sum with scale
+// log2(e), so lse is a pure function of the row's values: the same
+// logits give the same numbers in every batch row and on every rank.
+//
+//   1. max and NaN detect       degenerate rows answer NaN and stop;
+//   2. Z_q                      fused with the count histogram of the
+//                               key's high byte when N > 0;
+//   3. low-byte histogram       inside the chosen high bin -> tkey, the
+//                               key of the N-th largest value (0 when
+//                               N >= V: everything is above it);
+//   4. gather                   keys above tkey (fewer than N, any order,
+//                               LDS counter), then ties at tkey in index
+//                               order up to the remaining quota: per-wave
+//                               tie counts, a serial scan of the wave
+//                               totals, and each wave with a quota walks
+//                               its own segment with lane prefix counts;
+//   5. rank sort                the <= 20 distinct (key, idx) pairs.
+//
+// Loops are bounded by V, the 256 bins or LOGPROB_TOP.  Outputs are plain
+// vector stores; the only atomics are integer LDS adds.
+#define LOGPROB_TOP 20
+
+template <int NT>
+struct LogprobSmem {
+  u64 wsum[NT / WAVE];
+  float wmax[NT / WAVE];
+  int wnan[NT / WAVE];
+  unsigned wtie[NT / WAVE];
+  unsigned hcnt[256 * HR];
+  unsigned bcnt[256];
+  unsigned sel_digit;
+  unsigned sel_cnt;
+  unsigned gcount;
+  unsigned gkey[LOGPROB_TOP];
+  int gidx[LOGPROB_TOP];
+  double lse;
+};
+
+__device__ __forceinline__ float logprob_of(float l, double lse) {
+  return (float)((double)l - lse);
+}
+
+// One row with the whole block.  chosen is the token whose value goes to
+// *lp; n_top < 0 turns the row off (nothing read, nothing written),
+// n_top > LOGPROB_TOP counts as LOGPROB_TOP.  top_lp / top_id point at the
+// row's LOGPROB_TOP entries; all of them are written.
+template <int NT>
+__device__ __forceinline__ void logprob_row(
+    const unsigned short* __restrict__ row, int V, long long chosen,
+    int n_top, float* __restrict__ lp, float* __restrict__ top_lp,
+    int* __restrict__ top_id, LogprobSmem<NT>& sm) {
+  constexpr int NW = NT / WAVE;
+  if (n_top < 0) return;  // uniform over the block
+  const int N = n_top < LOGPROB_TOP ? n_top : LOGPROB_TOP;
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  const int seg = (int)((((long long)V + NW - 1) / NW + 2047) / 2048 * 2048);
+  const int iters = seg / 512;
+  const int base = wid * seg + lane * 8;
+  const bool vec_ok = ((unsigned long long)row & 15ull) == 0;
+  const float qnan = __builtin_nanf("");
+
+  // ---- 1. max and NaN detect -----------------------------------------
+  float best = -INFINITY;
+  int has_nan = 0;
+  row_pass(row, V, vec_ok, base, iters,
+           [&](int, unsigned short h, bool valid) {
+             const float v = bf2f(h);
+             if (valid && v > best) best = v;
+             has_nan |= (valid && v != v);
+           });
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    best = fmaxf(best, __shfl_xor(best, off, WAVE));
+    has_nan |= __shfl_xor(has_nan, off, WAVE);
+  }
+  if (lane == 0) {
+    sm.wmax[wid] = best;
+    sm.wnan[wid] = has_nan;
+  }
+  if (threadIdx.x == 0) sm.gcount = 0u;
+  __syncthreads();
+  best = sm.wmax[0];
+  has_nan = sm.wnan[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) {
+    best = fmaxf(best, sm.wmax[w]);
+    has_nan |= sm.wnan[w];
+  }
+  const float m = best;
+  if (has_nan || !(fabsf(m) < INFINITY)) {
+    if (threadIdx.x == 0) *lp = qnan;
+    if (threadIdx.x < LOGPROB_TOP) {
+      top_lp[threadIdx.x] = qnan;
+      top_id[threadIdx.x] = -1;
+    }
+    return;
+  }
+
+  // ---- 2./3. Z_q and the threshold key -------------------------------
+  // The sampler's radix walk with its top-k predicate "count at or above
+  // this digit >= N", counts only.  N < V here, so the predicate holds at
+  // digit 0 of either level and exactly one digit d has it while d + 1
+  // does not.
+  const float scale = 1.44269504088896340736f;
+  const bool walk = N > 0 && N < V;
+  const int copy = lane & (HR - 1);
+  unsigned prefix = 0;
+  unsigned cnt_above = 0;
+  u64 zq = 0;
+#pragma unroll 1
+  for (int level = 0; level < (walk ? 2 : 1); ++level) {
+    if (walk) {
+      for (int i = threadIdx.x; i < 256 * HR; i += NT) sm.hcnt[i] = 0u;
+      __syncthreads();
+    }
+    const int shift = level == 0 ? 8 : 0;
+    row_pass(row, V, vec_ok, base, iters,
+             [&](int, unsigned short h, bool valid) {
+               if (level == 0)
+                 zq += valid ? weight_q(bf2f(h), m, scale) : 0ull;
+               const unsigned key = bf_key(h);
+               if (walk && valid && (level == 0 || (key >> 8) == prefix))
+                 atomicAdd(&sm.hcnt[((key >> shift) & 255u) * HR + copy], 1u);
+             });
+    if (level == 0) {
+      zq = wave_sum_u64(zq);
+      if (lane == 0) sm.wsum[wid] = zq;
+    }
+    __syncthreads();
+    if (level == 0 && threadIdx.x == 0) {
+      u64 z = 0;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) z += sm.wsum[w];
+      // z >= 2^40: the maximum's own weight
+      sm.lse = (double)m + log((double)z * 9.094947017729282379150390625e-13);
+    }
+    if (!walk) break;
+    if (threadIdx.x < 256) {
+      unsigned c = 0;
+#pragma unroll
+      for (int r = 0; r < HR; ++r) c += sm.hcnt[threadIdx.x * HR + r];
+      sm.bcnt[threadIdx.x] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) {
+      const int d = threadIdx.x;
+      unsigned c0 = cnt_above, c1 = cnt_above;  // at or above d / d + 1
+      for (int e = 255; e >= 0; --e) {
+        const unsigned c = sm.bcnt[e];
+        if (e >= d) c0 += c;
+        if (e > d) c1 += c;
+      }
+      if (c0 >= (unsigned)N && c1 < (unsigned)N) {
+        sm.sel_digit = (unsigned)d;
+        sm.sel_cnt = c1;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | sm.sel_digit;
+    cnt_above = sm.sel_cnt;
+  }
+  __syncthreads();
+  const double lse = sm.lse;
+  const unsigned tkey = walk ? prefix : 0u;
+
+  // chosen token: bounds-checked, so an id outside [0, V) reads nothing
+  if (threadIdx.x == 0)
+    *lp = (chosen >= 0 && chosen < (long long)V)
+              ? logprob_of(bf2f(row[chosen]), lse)
+              : qnan;
+  if (N == 0) {
+    if (threadIdx.x < LOGPROB_TOP) {
+      top_lp[threadIdx.x] = qnan;
+      top_id[threadIdx.x] = -1;
+    }
+    return;
+  }
+
+  // ---- 4. gather --------------------------------------------------------
+  // Above tkey: cnt_above < N elements (all V <= N of them when the walk
+  // was skipped; every key of a NaN-free row is above 0).
+  unsigned ties = 0;
+  row_pass(row, V, vec_ok, base, iters,
+           [&](int j, unsigned short h, bool valid) {
+             const unsigned key = bf_key(h);
+             if (valid && key > tkey) {
+               const unsigned p = atomicAdd(&sm.gcount, 1u);
+               if (p < LOGPROB_TOP) {
+                 sm.gkey[p] = key;
+                 sm.gidx[p] = j;
+               }
+             }
+             ties += (walk && valid && key == tkey) ? 1u : 0u;
+           });
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) ties += __shfl_xor(ties, off, WAVE);
+  if (lane == 0) sm.wtie[wid] = ties;
+  __syncthreads();
+  const int total = walk ? N : V;  // entries reported: min(N, V)
+  if (walk) {
+    // Ties at tkey in index order: wave w's segment precedes wave w + 1's.
+    const unsigned quota = (unsigned)N - cnt_above;  // >= 1
+    unsigned before = 0;
+    for (int w = 0; w < wid; ++w) before += sm.wtie[w];
+    unsigned mine = 0;  // ties this wave admits
+    if (before < quota) {
+      mine = quota - before;
+      if (mine > sm.wtie[wid]) mine = sm.wtie[wid];
+    }
+    unsigned run = 0;  // ties of this wave before the current step
+    for (int it = 0; it < iters && run < mine; ++it) {
+      const int idx = base + it * 512;
+      const s16x8 x = load8(row, V, vec_ok, idx);
+      unsigned c = 0;
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        c += (idx + k < V && bf_key((unsigned short)x[k]) == tkey) ? 1u : 0u;
+      unsigned incl = c;
+#pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const unsigned o = __shfl_up(incl, off, WAVE);
+        if (lane >= off) incl += o;
+      }
+      unsigned r = run + incl - c;  // rank of this lane's first tie
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        if (idx + k < V && bf_key((unsigned short)x[k]) == tkey) {
+          if (r < mine) {
+            const unsigned p = cnt_above + before + r;  // < N
+            sm.gkey[p] = tkey;
+            sm.gidx[p] = idx + k;
+          }
+          ++r;
+        }
+      }
+      run += __shfl(incl, WAVE - 1, WAVE);
+    }
+  }
+  __syncthreads();
+
+  // ---- 5. rank sort and store -------------------------------------------
+  if (threadIdx.x < LOGPROB_TOP) {
+    const int t = threadIdx.x;
+    if (t < total) {
+      const unsigned key = sm.gkey[t];
+      const int idx = sm.gidx[t];
+      int rank = 0;
+      for (int s = 0; s < total; ++s) {
+        const unsigned ks = sm.gkey[s];
+        rank += (ks > key || (ks == key && sm.gidx[s] < idx)) ? 1 : 0;
+      }
+      top_lp[rank] = logprob_of(key_value(key), lse);
+      top_id[rank] = idx;
+    } else {
+      top_lp[t] = qnan;
+      top_id[t] = -1;
+    }
+  }
+}
+
+// logits [n, V], ids int64 [n], n_top int32 [n] -> lp fp32 [n],
+// top_lp fp32 [n, 20], top_ids int32 [n, 20].
+template <int NT>
+__global__ __launch_bounds__(NT) void token_logprobs_kernel(
+    const unsigned short* __restrict__ logits, int V,
+    const long long* __restrict__ ids, const int* __restrict__ n_top,
+    float* __restrict__ lp, float* __restrict__ top_lp,
+    int* __restrict__ top_ids) {
+  __shared__ LogprobSmem<NT> sm;
+  const long long i = blockIdx.x;
+  logprob_row<NT>(logits + i * V, V, ids[i], n_top[i], lp + i,
+                  top_lp + i * LOGPROB_TOP, top_ids + i * LOGPROB_TOP, sm);
+}
+
+// The in-graph form, launched after the advance kernel and before the
+// ctr increment: the chosen token is stage[0], which the advance kernel
+// has just written, and the ring row is the one it stored its token in.
+// stage is only read.
+template <int NT>
+__global__ __launch_bounds__(NT) void decode_logprobs_kernel(
+    const unsigned short* __restrict__ logits, int V,
+    const int* __restrict__ stage, long long b,
+    const int* __restrict__ n_top, float* __restrict__ lp_ring,
+    float* __restrict__ top_lp_ring, int* __restrict__ top_id_ring,
+    const long long* __restrict__ ctr, int chunk) {
+  __shared__ LogprobSmem<NT> sm;
+  const long long i = blockIdx.x;
+  long long slot = *ctr % chunk;
+  if (slot < 0) slot += chunk;
+  const long long o = slot * b + i;
+  logprob_row<NT>(logits + i * V, V, (long long)stage[i], n_top[i],
+                  lp_ring + o, top_lp_ring + o * LOGPROB_TOP,
+                  top_id_ring + o * LOGPROB_TOP, sm);
+}
+
+extern "C" void token_logprobs_launch(const void* logits, int V, long long n,
+                                      const void* ids, const void* n_top,
+                                      void* lp, void* top_lp, void* top_ids,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(token_logprobs_kernel<SAMPLE_THREADS>, dim3((unsigned)n),
+                     dim3(SAMPLE_THREADS), 0, stream,
+                     (const unsigned short*)logits, V, (const long long*)ids,
+                     (const int*)n_top, (float*)lp, (float*)top_lp,
+                     (int*)top_ids);
+}
+
+extern "C" void decode_logprobs_launch(const void* logits, int V,
+                                       const void* stage, long long b,
+                                       const void* n_top, void* lp_ring,
+                                       void* top_lp_ring, void* top_id_ring,
+                                       const void* ctr, int chunk,
+                                       hipStream_t stream) {
+  hipLaunchKernelGGL(decode_logprobs_kernel<SAMPLE_THREADS>,
+                     dim3((unsigned)b), dim3(SAMPLE_THREADS), 0, stream,
+                     (const unsigned short*)logits, V, (const int*)stage, b,
+                     (const int*)n_top, (float*)lp_ring, (float*)top_lp_ring,
+                     (int*)top_id_ring, (const long long*)ctr, chunk);
+}

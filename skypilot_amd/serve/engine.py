@@ -18,6 +18,13 @@ top-k, top-p, a per-request seed) instead of the host's torch sampler:
 sampled requests then chain graph replays like greedy ones, and a
 request's token at a position depends only on its seed, the position
 and the logits.
+
+With ``max_logprobs`` > 0, requests may ask for log-probabilities
+(``Request.logprobs`` / ``prompt_logprobs``): the model's raw
+distribution, temperature 1 and no filter, whatever the request samples
+with (ops.token_logprobs; docs/KERNELS.md "Token log-probabilities").
+In the graph path ops.decode_logprobs is captured behind the advance
+kernel and its rings are read in the chunk's one sync.
 """
 from __future__ import annotations
 
@@ -29,7 +36,7 @@ import threading
 import time
 import uuid
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -64,6 +71,9 @@ class InferenceContext:
     append_slots_l: Optional[list] = None
     append_start_l: Optional[list] = None
     append_lens_l: Optional[list] = None
+    # append: return the logits of every row, [n, sq, V], instead of the
+    # last valid row's [n, 1, V] (prompt log-probabilities)
+    all_rows: bool = False
     # fp8 cache, whole-prompt prefill: (slots, starts, lens) int32 device
     # tensors of the batch's cache write, built by the first layer
     kv_write_idx: Optional[tuple] = None
@@ -82,9 +92,21 @@ class Request:
     top_k: int = 0
     seed: Optional[int] = None
     stop_id: Optional[int] = None
+    # Log-probabilities need Engine(max_logprobs=N).  logprobs: how many
+    # alternatives per generated token (0: the chosen token only, at most
+    # N); prompt_logprobs: also score the prompt's own tokens.
+    logprobs: Optional[int] = None
+    prompt_logprobs: bool = False
     stream_queue: Optional["queue.Queue"] = None  # per-token streaming
     id: str = field(default_factory=lambda: uuid.uuid4().hex[:12])
     out_ids: List[int] = field(default_factory=list)
+    # results, aligned with out_ids: the chosen token's log-probability
+    # and the top `logprobs` (id, log-probability) pairs
+    out_logprobs: List[float] = field(default_factory=list)
+    out_top: List[List[Tuple[int, float]]] = field(default_factory=list)
+    # prompt_lps[i]: log-probability of prompt_ids[i] given the tokens
+    # before it; entry 0 is None
+    prompt_lps: List[Optional[float]] = field(default_factory=list)
     done: threading.Event = field(default_factory=threading.Event)
     created: float = field(default_factory=time.time)
     first_token_at: Optional[float] = None
@@ -107,7 +129,17 @@ class Engine:
                  tp_rank: int = 0, tp_world: int = 1,
                  prefill_chunk: Optional[int] = None,
                  device_sampling: bool = False,
-                 kv_dtype: str = "bf16"):
+                 kv_dtype: str = "bf16", max_logprobs: int = 0):
+        # 0 keeps the decode graph and the staged block as they are
+        # without the feature; N > 0 adds the log-probability kernel to
+        # the graph and lets a request ask for up to N alternatives.
+        if (isinstance(max_logprobs, bool)
+                or not isinstance(max_logprobs, int)
+                or not 0 <= max_logprobs <= ops.LOGPROB_TOP):
+            raise ValueError(
+                f"max_logprobs must be an int in [0, {ops.LOGPROB_TOP}], "
+                f"got {max_logprobs!r}")
+        self.max_logprobs = max_logprobs
         # "fp8" stores the KV cache as e4m3fn rows with power-of-two row
         # scales (docs/KERNELS.md "FP8 KV cache"): 129 instead of 256
         # bytes per (token, kv head) row.
@@ -224,6 +256,7 @@ class Engine:
     # ------------------------------------------------------------------
     def submit(self, req: Request) -> Request:
         self._check_sampling(req)
+        self._check_logprobs(req)
         if len(req.prompt_ids) >= self.max_seq:
             req.prompt_ids = req.prompt_ids[-(self.max_seq - 1 -
                                               req.max_tokens):]
@@ -267,6 +300,62 @@ class Engine:
         if req.seed is None:
             req.seed = random.getrandbits(63)
         req.seed %= 1 << 63
+
+    def _check_logprobs(self, req: Request) -> None:
+        """Validate a request's log-probability fields against
+        max_logprobs.  Raises ValueError."""
+        n = req.logprobs
+        if n is not None and (isinstance(n, bool) or not isinstance(n, int)
+                              or n < 0):
+            raise ValueError(
+                f"logprobs must be None or an int >= 0, got {n!r}")
+        if not isinstance(req.prompt_logprobs, bool):
+            raise ValueError("prompt_logprobs must be a bool, got "
+                             f"{req.prompt_logprobs!r}")
+        if n is None and not req.prompt_logprobs:
+            return
+        if self.max_logprobs == 0:
+            raise ValueError(
+                "logprobs and prompt_logprobs need an engine with "
+                "log-probabilities on (Engine(max_logprobs=N) / "
+                "--max-logprobs N)")
+        if n is not None and n > self.max_logprobs:
+            raise ValueError(
+                f"logprobs = {n} exceeds this engine's max_logprobs = "
+                f"{self.max_logprobs}")
+
+    def _record_logprobs(self, logits: torch.Tensor, reqs: List[Request],
+                         ids: List[int]) -> None:
+        """Append out_logprobs / out_top for the tokens `ids` chosen from
+        `logits` [n, V], for the requests that asked: first tokens after
+        a prefill and every token of the eager decode step."""
+        rows = [i for i, r in enumerate(reqs) if r.logprobs is not None]
+        if not rows:
+            return
+        lp, tlp, tid = ops.token_logprobs(
+            logits[rows].contiguous(), [ids[i] for i in rows],
+            [reqs[i].logprobs for i in rows])
+        lp, tlp, tid = lp.tolist(), tlp.tolist(), tid.tolist()
+        for j, i in enumerate(rows):
+            self._append_logprobs(reqs[i], lp[j], tid[j], tlp[j])
+
+    @staticmethod
+    def _append_logprobs(req: Request, lp: float, top_ids: List[int],
+                         top_lps: List[float]) -> None:
+        req.out_logprobs.append(lp)
+        req.out_top.append([(t, v) for t, v in zip(top_ids, top_lps)
+                            if t >= 0][:req.logprobs])
+
+    def _record_prompt_logprobs(self, req: Request, logits: torch.Tensor,
+                                ids: List[int]) -> None:
+        """Extend req.prompt_lps by the log-probabilities of the prompt
+        tokens `ids` under `logits` [len(ids), V], row j being the logits
+        of the position before ids[j]."""
+        if not req.prompt_lps:
+            req.prompt_lps.append(None)
+        if ids:
+            lp, _, _ = ops.token_logprobs(logits.contiguous(), ids, 0)
+            req.prompt_lps.extend(lp.tolist())
 
     def generate(self, prompt_ids: List[int], max_tokens: int = 64,
                  temperature: float = 0.0,
@@ -316,6 +405,11 @@ class Engine:
         logits = self.model(toks, positions, ctx)
         last = logits[torch.arange(n), torch.tensor(lens) - 1]  # [n, V]
         first = self._sample_batch(last, reqs, [l - 1 for l in lens])
+        self._record_logprobs(last, reqs, first)
+        for i, req in enumerate(reqs):
+            if req.prompt_logprobs:
+                self._record_prompt_logprobs(
+                    req, logits[i, :lens[i] - 1], req.prompt_ids[1:])
         for i, (req, slot) in enumerate(zip(reqs, slots)):
             next_id = first[i]
             self.cache.lens[slot] = lens[i]
@@ -329,11 +423,15 @@ class Engine:
 
     # -------------------------- chunked prefill ------------------------
     @torch.no_grad()
-    def _append_forward(self, slots, starts, lens, chunks) -> torch.Tensor:
+    def _append_forward(self, slots, starts, lens, chunks,
+                        all_rows: bool = False) -> torch.Tensor:
         """One append forward: sequence i adds tokens chunks[i] (lens[i]
         of them) at positions starts[i].. to cache slot slots[i].
-        Returns the logits of each sequence's last valid row, [n, 1, V].
-        The leader and the TP followers run exactly this."""
+        Returns the logits of each sequence's last valid row, [n, 1, V],
+        or with `all_rows` those of every row, [n, sq, V].  The leader
+        and the TP followers run exactly this; only the leader sets
+        all_rows (the lm_head is replicated and follows the last
+        collective, so the followers need not)."""
         n = len(slots)
         sq = max(64, (max(lens) + 63) // 64 * 64)
         toks = torch.zeros(n, sq, dtype=torch.long, device=self.device)
@@ -353,7 +451,7 @@ class Engine:
             cache=self.cache, mode="append", append_slots=i32(slots),
             append_start=start_t, append_lens=i32(lens),
             append_slots_l=list(slots), append_start_l=list(starts),
-            append_lens_l=list(lens))
+            append_lens_l=list(lens), all_rows=all_rows)
         return self.model(toks, positions, ctx)
 
     @torch.no_grad()
@@ -370,13 +468,29 @@ class Engine:
                   for e, s, l in zip(batch, starts, lens)]
         self._tp_bcast({"op": "append", "slots": slots, "starts": starts,
                         "lens": lens, "chunks": chunks})
-        logits = self._append_forward(slots, starts, lens, chunks)
+        all_rows = any(e.req.prompt_logprobs for e in batch)
+        logits = self._append_forward(slots, starts, lens, chunks, all_rows)
         ends = [s + l for s, l in zip(starts, lens)]
+        if all_rows:
+            # Row j of a chunk predicts the prompt token at start + j + 1;
+            # the chunk's last valid row predicts the next chunk's first
+            # token, or past the prompt the token sampled below.
+            for i, e in enumerate(batch):
+                if e.req.prompt_logprobs:
+                    ids = e.req.prompt_ids[starts[i] + 1:ends[i] + 1]
+                    self._record_prompt_logprobs(
+                        e.req, logits[i, :len(ids)], ids)
+            logits = logits[torch.arange(len(batch)),
+                            torch.tensor(lens) - 1].unsqueeze(1)
         fin = [i for i, e in enumerate(batch)
                if ends[i] >= len(e.req.prompt_ids)]
-        first = dict(zip(fin, self._sample_batch(
-            logits[fin, 0], [batch[i].req for i in fin],
-            [ends[i] - 1 for i in fin]))) if fin else {}
+        first = {}
+        if fin:
+            fin_reqs = [batch[i].req for i in fin]
+            fin_ids = self._sample_batch(logits[fin, 0], fin_reqs,
+                                         [ends[i] - 1 for i in fin])
+            self._record_logprobs(logits[fin, 0], fin_reqs, fin_ids)
+            first = dict(zip(fin, fin_ids))
         for i, e in enumerate(batch):
             e.done += lens[i]
             self.stats["prefill_tokens"] += lens[i]
@@ -419,14 +533,20 @@ class Engine:
         # (temperature bits, top_p bits, top_k, seed_lo, seed_hi), so
         # they change between replays without a recapture and ride in
         # the same copy.
-        rows = 11 if self.device_sampling else 6
+        # With max_logprobs > 0 one more row at the end holds each
+        # sequence's n_top (-1: did not ask, and padding).
+        rows = (11 if self.device_sampling else 6) + (
+            1 if self.max_logprobs else 0)
         st = {
             "host": torch.zeros(rows, b, dtype=torch.int32,
                                 pin_memory=True),
             "block": torch.zeros(rows, b, dtype=torch.int32, device=dev),
         }
         st["stage"] = st["block"][:6]
-        st["samp"] = st["block"][6:]
+        st["samp"] = st["block"][6:11 if self.device_sampling else 6]
+        if self.max_logprobs:
+            st["ntop"] = st["block"][rows - 1]
+            st["ntop"].fill_(-1)
         st["stage"][2] = self._scratch_slot
         st["stage"][5] = self._scratch_slot
         st["stage"][4] = 1
@@ -449,6 +569,14 @@ class Engine:
         st["ring"] = torch.zeros(self.CHUNK, b, dtype=torch.long,
                                  device=dev)
         st["ctr"] = torch.zeros(1, dtype=torch.long, device=dev)
+        if self.max_logprobs:
+            top = ops.LOGPROB_TOP
+            st["lp_ring"] = torch.zeros(self.CHUNK, b, dtype=torch.float32,
+                                        device=dev)
+            st["top_lp_ring"] = torch.zeros(
+                self.CHUNK, b, top, dtype=torch.float32, device=dev)
+            st["top_id_ring"] = torch.zeros(
+                self.CHUNK, b, top, dtype=torch.int32, device=dev)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             toks, positions, ctx = unpack()
@@ -468,6 +596,14 @@ class Engine:
             else:
                 ops.decode_advance(st["out"][:, 0], st["stage"],
                                    st["ring"], st["ctr"])
+            # Log-probabilities of the token just chosen (stage[0]), from
+            # the same logits, into ring row ctr % CHUNK: after the
+            # advance kernel and before the ctr increment.
+            if self.max_logprobs:
+                ops.decode_logprobs(st["out"][:, 0], st["stage"],
+                                    st["ntop"], st["lp_ring"],
+                                    st["top_lp_ring"], st["top_id_ring"],
+                                    st["ctr"])
             st["ctr"] += 1
         self._graphs[b] = (g, st)
         self.stats["graph_buckets"] = sorted(self._graphs)
@@ -497,9 +633,16 @@ class Engine:
             # warmup forwards contain all-reduces that need every rank
             # participating (the follower captures on receipt).
             samp = self._samp_rows(reqs)
+            # n_top per row for the in-graph log-probabilities; a batch
+            # the host samples from takes them from the logits below
+            ntop = None
+            if self.max_logprobs:
+                ntop = [r.logprobs if chain and r.logprobs is not None
+                        else -1 for r in reqs]
+            want_lp = ntop is not None and any(v >= 0 for v in ntop)
             self._tp_bcast({"op": "decode", "graph": True, "bucket": b,
                             "slots": slots, "lens": lens, "toks": tok_l,
-                            "chunk": chunk, "samp": samp})
+                            "chunk": chunk, "samp": samp, "ntop": ntop})
             try:
                 g, st = self._get_graph(b)
             except Exception as e:  # capture unsupported -> eager forever
@@ -510,11 +653,15 @@ class Engine:
                       f"to eager decode: {e!r}", file=sys.stderr)
                 self.use_graphs = False
                 return self._decode_step()
-            self._stage_inputs(st, slots, lens, tok_l, samp)
+            self._stage_inputs(st, slots, lens, tok_l, samp, ntop)
             for _ in range(chunk):
                 g.replay()
             if chain:
                 ring = st["ring"][:chunk, :n].tolist()  # one sync/chunk
+                if want_lp:  # same sync: the replays have finished
+                    lp_r = st["lp_ring"][:chunk, :n].tolist()
+                    tlp_r = st["top_lp_ring"][:chunk, :n].tolist()
+                    tid_r = st["top_id_ring"][:chunk, :n].tolist()
                 for t in range(chunk):
                     for i, slot in enumerate(slots):
                         if slot not in self.active:  # finished earlier t
@@ -523,6 +670,9 @@ class Engine:
                         next_id = ring[t][i]
                         self.cache.lens[slot] += 1
                         req.out_ids.append(next_id)
+                        if req.logprobs is not None:
+                            self._append_logprobs(req, lp_r[t][i],
+                                                  tid_r[t][i], tlp_r[t][i])
                         if req.stream_queue is not None:
                             req.stream_queue.put(next_id)
                         self.stats["tokens_generated"] += 1
@@ -557,14 +707,14 @@ class Engine:
             batch_ids = self._sample_batch(logits[:n, 0], reqs, lens)
         elif all(r.temperature == 0 for r in reqs):
             batch_ids = logits[:n, 0].argmax(-1).tolist()
+        if batch_ids is None:
+            batch_ids = [self._sample(logits[i, 0], r.temperature, r.top_p)
+                         for i, r in enumerate(reqs)]
+        self._record_logprobs(logits[:n, 0], reqs, batch_ids)
         for i, slot in enumerate(slots):
             self.cache.lens[slot] += 1
             req = self.active[slot]
-            if batch_ids is not None:
-                next_id = batch_ids[i]
-            else:
-                next_id = self._sample(logits[i, 0], req.temperature,
-                                       req.top_p)
+            next_id = batch_ids[i]
             req.out_ids.append(next_id)
             if req.stream_queue is not None:
                 req.stream_queue.put(next_id)
@@ -578,7 +728,8 @@ class Engine:
             return None
         return [(r.temperature, r.top_p, r.top_k, r.seed) for r in reqs]
 
-    def _stage_inputs(self, st, slots, lens, tok_l, samp) -> None:
+    def _stage_inputs(self, st, slots, lens, tok_l, samp,
+                      ntop=None) -> None:
         """Fill the pinned host block for one graph step and start its
         copy to the device (the leader and the TP followers share this).
         Padding rows point at the scratch slot and are greedy."""
@@ -603,6 +754,9 @@ class Engine:
             hu[9, :n] = [r[3] & 0xFFFFFFFF for r in samp]
             hu[10, :n] = [r[3] >> 32 for r in samp]
             h[6:, n:] = 0  # temperature 0: padding rows take the argmax
+        if self.max_logprobs:
+            h[-1, :n] = ntop if ntop is not None else -1
+            h[-1, n:] = -1
         st["ctr"].zero_()
         st["block"].copy_(st["host"], non_blocking=True)
 
@@ -695,7 +849,8 @@ class Engine:
         slots, lens, tok_l = msg["slots"], msg["lens"], msg["toks"]
         if msg["graph"]:
             g, st = self._get_graph(msg["bucket"])
-            self._stage_inputs(st, slots, lens, tok_l, msg.get("samp"))
+            self._stage_inputs(st, slots, lens, tok_l, msg.get("samp"),
+                               msg.get("ntop"))
             for _ in range(msg["chunk"]):
                 g.replay()
             torch.cuda.synchronize()

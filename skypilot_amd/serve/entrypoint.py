@@ -14,6 +14,7 @@ bundled trainer can be loaded with --checkpoint-dir.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import time
 from typing import List, Optional
@@ -37,6 +38,24 @@ class ByteTokenizer:
         return bytes(i for i in ids if 0 <= i < 256).decode(
             "utf-8", errors="replace")
 
+    def token(self, i: int) -> str:
+        """One token as a string that names it uniquely (the keys of a
+        top_logprobs entry): the character for ASCII, ``bytes:\\xNN`` for
+        a byte that is no text on its own, ``<|id|>`` for the rest."""
+        if 0 <= i < 128:
+            return chr(i)
+        if i < 256:
+            return f"bytes:\\x{i:02x}"
+        return f"<|{i}|>"
+
+    def token_bytes(self, i: int) -> List[int]:
+        return [i] if 0 <= i < 256 else []
+
+
+def _num(v: Optional[float]) -> Optional[float]:
+    """A log-probability for JSON: -inf and NaN become null."""
+    return v if v is not None and math.isfinite(v) else None
+
 
 class CompletionRequest(BaseModel):
     model: str = ""
@@ -48,6 +67,11 @@ class CompletionRequest(BaseModel):
     seed: Optional[int] = None
     stop: Optional[List[str]] = None
     stream: bool = False
+    # number of alternatives per token (0: the chosen token only); needs
+    # a server started with --max-logprobs
+    logprobs: Optional[int] = None
+    # prefix the text with the prompt; with logprobs also score its tokens
+    echo: bool = False
 
 
 class ChatMessage(BaseModel):
@@ -63,6 +87,8 @@ class ChatRequest(BaseModel):
     top_p: float = 1.0
     top_k: int = 0
     seed: Optional[int] = None
+    logprobs: bool = False
+    top_logprobs: Optional[int] = None
 
 
 def create_app(engine: Engine, model_name: str) -> FastAPI:
@@ -84,12 +110,13 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
         return {"object": "list",
                 "data": [{"id": model_name, "object": "model"}]}
 
-    def _complete(prompt: str, req):
+    def _complete(prompt: str, req, logprobs=None, prompt_logprobs=False):
         ids = tok.encode(prompt)
         t0 = time.time()
         r = Request(prompt_ids=ids, max_tokens=req.max_tokens,
                     temperature=req.temperature, top_p=req.top_p,
-                    top_k=req.top_k, seed=req.seed)
+                    top_k=req.top_k, seed=req.seed, logprobs=logprobs,
+                    prompt_logprobs=prompt_logprobs)
         try:
             engine.submit(r)
         except ValueError as e:
@@ -98,7 +125,28 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
             raise HTTPException(status_code=504,
                                 detail="generation timed out")
         # r.seed: the seed the device sampler used (None on the host path)
-        return r.out_ids, time.time() - t0, len(ids), r.seed
+        return r, time.time() - t0
+
+    def _top_dict(top):
+        # value-descending; ids are distinct, and so are their names
+        return {tok.token(t): _num(v) for t, v in top}
+
+    def _completion_logprobs(r, n_out: int, echo: bool):
+        """The `logprobs` object of /v1/completions for the first n_out
+        generated tokens, after the prompt's when `echo`.  Prompt tokens
+        carry their own log-probability (null for the first) and no
+        alternatives."""
+        ids = list(r.out_ids[:n_out])
+        lps = [_num(v) for v in r.out_logprobs[:n_out]]
+        tops = [_top_dict(t) for t in r.out_top[:n_out]]
+        if echo:
+            ids = list(r.prompt_ids) + ids
+            lps = [_num(v) for v in r.prompt_lps] + lps
+            tops = [None] * len(r.prompt_ids) + tops
+        return {"tokens": [tok.token(i) for i in ids],
+                "token_logprobs": lps, "top_logprobs": tops,
+                "text_offset": [len(tok.decode(ids[:k]))
+                                for k in range(len(ids))]}
 
     @app.post("/v1/completions")
     def completions(req: CompletionRequest):
@@ -112,41 +160,64 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
             r = _Req(prompt_ids=tok.encode(req.prompt),
                      max_tokens=req.max_tokens,
                      temperature=req.temperature, top_p=req.top_p,
-                     top_k=req.top_k, seed=req.seed, stream_queue=q)
+                     top_k=req.top_k, seed=req.seed, stream_queue=q,
+                     logprobs=req.logprobs)
             try:
                 engine.submit(r)
             except ValueError as e:
                 raise HTTPException(status_code=400, detail=str(e))
 
             def sse():
+                k = 0  # index of the token in r.out_ids
                 while True:
                     item = q.get(timeout=600)
                     if item is None:
                         yield "data: [DONE]\n\n"
                         return
+                    choice = {"index": 0, "text": tok.decode([item]),
+                              "finish_reason": None}
+                    if req.logprobs is not None:
+                        # the engine appends a token's entry before it
+                        # queues the token
+                        choice["logprobs"] = {
+                            "tokens": [tok.token(item)],
+                            "token_logprobs": [_num(r.out_logprobs[k])],
+                            "top_logprobs": [_top_dict(r.out_top[k])],
+                            "text_offset": [len(tok.decode(r.out_ids[:k]))]}
+                    k += 1
                     chunk = {"id": "cmpl-local",
                              "object": "text_completion",
                              "model": model_name,
-                             "choices": [{"index": 0,
-                                          "text": tok.decode([item]),
-                                          "finish_reason": None}]}
+                             "choices": [choice]}
                     yield f"data: {_json.dumps(chunk)}\n\n"
 
             return StreamingResponse(sse(), media_type="text/event-stream")
-        out, dt, n_prompt, seed = _complete(req.prompt, req)
+        r, dt = _complete(
+            req.prompt, req, logprobs=req.logprobs,
+            prompt_logprobs=req.echo and req.logprobs is not None)
+        out, n_prompt, seed = r.out_ids, len(r.prompt_ids), r.seed
         text = tok.decode(out)
         finish = "length"
+        n_kept = len(out)
         for stop in req.stop or []:
             i = text.find(stop)
             if i >= 0:
                 text = text[:i]
                 finish = "stop"
+                # the tokens whose text survives: those that begin
+                # before the cut
+                n_kept = sum(len(tok.decode(out[:k])) < i
+                             for k in range(len(out)))
                 break
+        choice = {"index": 0, "text": text, "finish_reason": finish}
+        if req.echo:
+            choice["text"] = tok.decode(r.prompt_ids) + text
+        if req.logprobs is not None:
+            choice["logprobs"] = _completion_logprobs(r, n_kept, req.echo)
         return {
             "id": "cmpl-local", "object": "text_completion",
             "model": model_name, "seed": seed,
-            "choices": [{"index": 0, "text": text,
-                         "finish_reason": finish}],
+            "choices": [choice],
             "usage": {"prompt_tokens": n_prompt,
                       "completion_tokens": len(out),
                       "total_tokens": n_prompt + len(out),
@@ -156,14 +227,28 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
     @app.post("/v1/chat/completions")
     def chat(req: ChatRequest):
         prompt = "\n".join(f"{m.role}: {m.content}" for m in req.messages)
-        out, dt, n_prompt, seed = _complete(prompt, req)
+        if req.top_logprobs is not None and not req.logprobs:
+            raise HTTPException(status_code=400,
+                                detail="top_logprobs needs logprobs: true")
+        r, dt = _complete(
+            prompt, req,
+            logprobs=(req.top_logprobs or 0) if req.logprobs else None)
+        out, n_prompt, seed = r.out_ids, len(r.prompt_ids), r.seed
+        choice = {"index": 0,
+                  "message": {"role": "assistant",
+                              "content": tok.decode(out)},
+                  "finish_reason": "length"}
+        if req.logprobs:
+            def entry(t, v):
+                return {"token": tok.token(t), "logprob": _num(v),
+                        "bytes": tok.token_bytes(t)}
+            choice["logprobs"] = {"content": [
+                {**entry(t, v), "top_logprobs": [entry(*p) for p in top]}
+                for t, v, top in zip(out, r.out_logprobs, r.out_top)]}
         return {
             "id": "chatcmpl-local", "object": "chat.completion",
             "model": model_name, "seed": seed,
-            "choices": [{"index": 0,
-                         "message": {"role": "assistant",
-                                     "content": tok.decode(out)},
-                         "finish_reason": "length"}],
+            "choices": [choice],
             "usage": {"prompt_tokens": n_prompt,
                       "completion_tokens": len(out),
                       "total_tokens": n_prompt + len(out),
@@ -190,6 +275,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="draw tokens with the seeded sampling kernel "
                          "(needed for top_k and seed; sampled requests "
                          "chain graph replays like greedy ones)")
+    ap.add_argument("--max-logprobs", type=int, default=0,
+                    help="let requests ask for token log-probabilities "
+                         "with up to this many alternatives per token "
+                         "(at most 20); 0, the default, leaves them off")
     ap.add_argument("--device", default=None)
     ap.add_argument("--fp8-decode", action="store_true",
                     help="quantize weights to rowwise e4m3fn for the "
@@ -231,7 +320,8 @@ def main():
                         tp_rank=rank, tp_world=args.tp,
                         prefill_chunk=args.prefill_chunk,
                         device_sampling=args.device_sampling,
-                        kv_dtype=args.kv_dtype)
+                        kv_dtype=args.kv_dtype,
+                        max_logprobs=args.max_logprobs)
         if args.fp8_decode:
             engine.enable_fp8_decode()
         if rank > 0:
@@ -249,7 +339,8 @@ def main():
                     max_batch=args.max_batch,
                     prefill_chunk=args.prefill_chunk,
                     device_sampling=args.device_sampling,
-                    kv_dtype=args.kv_dtype)
+                    kv_dtype=args.kv_dtype,
+                        max_logprobs=args.max_logprobs)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode()
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
