@@ -194,7 +194,7 @@ extern "C" __global__ __launch_bounds__(256, 2) void attn_fwd_swapped_kernel(
         int src = (2 * (lgrp & 1) + (j >> 2)) * 16 + lrow;
         float v0 = __shfl(st_acc[2 * ks][j & 3], src, 64);
         float v1 = __shfl(st_acc[2 * ks + 1][j & 3], src, 64);
-        p_b[ks][j] = (short)f2bf_trunc((lgrp >> 1) ? v1 : v0);
+        p_b[ks][j] = (short)f2bf((lgrp >> 1) ? v1 : v0);
       }
     }
 

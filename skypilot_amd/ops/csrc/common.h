@@ -120,9 +120,11 @@ __device__ __forceinline__ void bf8_to_f32(const s16x8 v, float* out) {
   for (int i = 0; i < 8; ++i) out[i] = bf2f((unsigned short)v[i]);
 }
 
-// Truncating f32->bf16 (no rounding): for values already carrying
-// >=bf16 rounding error (attention probabilities), saves ~4 VALU ops
-// per element on the hot softmax->LDS path.
+// Truncating f32->bf16 (no rounding): only for values that are exact in
+// bf16 already (the fp8 KV decode, kv_fp8.h).  Attention probabilities
+// are rounded with f2bf: truncation pulls every weight down by half an
+// ulp on average, a bias of -2.4e-3 in O and dV
+// (tests/test_attn_train_gpu.py, test_rounding_bias_*).
 __device__ __forceinline__ unsigned short f2bf_trunc(float f) {
   union { float f; unsigned int u; } v;
   v.f = f;
