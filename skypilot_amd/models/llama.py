@@ -188,13 +188,20 @@ class Attention(nn.Module):
             # attended from registers; the cache row is written for
             # future steps by one block per kv head).
             li = self.layer_idx
+            # Engine(decode_attn="grouped"): the same contract from the
+            # grouped split-KV kernel (attention_decode_gqa.hip)
+            grouped = infer_ctx.decode_attn == "grouped"
             if cache.kv_dtype == "fp8":
-                o = ops.attn_decode_qkv_fp8(
+                fn = (ops.attn_decode_qkv_gqa_fp8 if grouped
+                      else ops.attn_decode_qkv_fp8)
+                o = fn(
                     qkv, cache.k[li], cache.v[li], cache.k_exp[li],
                     cache.v_exp[li], cos, sin, positions, infer_ctx.kv_lens,
                     infer_ctx.slot_ids_i32, self.n_q, self.n_kv, self.scale)
             else:
-                o = ops.attn_decode_qkv(
+                fn = ops.attn_decode_qkv_gqa if grouped \
+                    else ops.attn_decode_qkv
+                o = fn(
                     qkv, cache.k[li], cache.v[li], cos, sin, positions,
                     infer_ctx.kv_lens, infer_ctx.slot_ids_i32, self.n_q,
                     self.n_kv, self.scale)

@@ -1024,6 +1024,43 @@ def attn_decode_qkv(qkv, kc, vc, cos, sin, positions, kv_lens, slot_ids,
     return attn_decode(q, kc, vc, kv_lens, slot_ids, scale)
 
 
+GQA_MAX_GROUP = 16  # q heads per kv head the grouped decode kernel takes
+
+
+def attn_decode_qkv_gqa(qkv, kc, vc, cos, sin, positions, kv_lens, slot_ids,
+                        Hq, Hkv, scale, split_rows=-1):
+    """attn_decode_qkv by the grouped split-KV kernel
+    (attention_decode_gqa.hip): one block per (sequence, kv head, kv
+    range), the group's q heads as the N dimension of an MFMA, so each K/V
+    row is read once; a combine kernel merges the kv ranges.  split_rows
+    (rows per range) is -1 for the built-in constant or a positive
+    multiple of 128.  Same contract and cache effect as attn_decode_qkv;
+    the CPU path is attn_decode_qkv's."""
+    if qkv.is_cuda:
+        C = _require_native("attn_decode_qkv_gqa")
+        return C.attn_decode_qkv_gqa(qkv.contiguous(), kc, vc, cos, sin,
+                                     positions.int(), kv_lens.int(),
+                                     slot_ids.int(), Hq, Hkv, scale,
+                                     split_rows)
+    return attn_decode_qkv(qkv, kc, vc, cos, sin, positions, kv_lens,
+                           slot_ids, Hq, Hkv, scale)
+
+
+def attn_decode_qkv_gqa_fp8(qkv, kc, vc, ke, ve, cos, sin, positions,
+                            kv_lens, slot_ids, Hq, Hkv, scale,
+                            split_rows=-1):
+    """attn_decode_qkv_fp8 by the grouped split-KV kernel; the CPU path is
+    attn_decode_qkv_fp8's."""
+    if qkv.is_cuda:
+        C = _require_native("attn_decode_qkv_gqa_fp8")
+        return C.attn_decode_qkv_gqa_fp8(qkv.contiguous(), kc, vc, ke, ve,
+                                         cos, sin, positions.int(),
+                                         kv_lens.int(), slot_ids.int(), Hq,
+                                         Hkv, scale, split_rows)
+    return attn_decode_qkv_fp8(qkv, kc, vc, ke, ve, cos, sin, positions,
+                               kv_lens, slot_ids, Hq, Hkv, scale)
+
+
 def rope_kvwrite(qkv, kc, vc, cos, sin, positions, slot_ids, Hq, Hkv):
     """Packed-qkv rope + KV-cache scatter (decode_fused.hip): applies
     rope to the q and k segments of qkv [n, (Hq+2*Hkv)*D], writes the
@@ -1054,4 +1091,5 @@ __all__ = [
     "attn_append", "attn_append_ref",
     "kv_quantize", "kv_dequantize", "kv_write_fp8", "attn_decode_qkv_fp8",
     "attn_append_fp8", "attn_decode_fp8",
+    "attn_decode_qkv_gqa", "attn_decode_qkv_gqa_fp8",
 ]

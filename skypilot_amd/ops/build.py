@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "attention_bwd_v3.hip",
     "attention_decode.hip",
     "attention_decode_fp8.hip",
+    "attention_decode_gqa.hip",
     "attention_append.hip",
     "kv_write_fp8.hip",
     "swiglu.hip",
@@ -39,6 +40,13 @@ HIP_SOURCES = [
     "mfma_probe.hip",
 ]
 CPP_SOURCES = ["bindings.cpp"]
+# Extra flags per device TU.  The grouped decode kernel is built without
+# packed-fp32 instructions (v_pk_mul_f32 and kin): its fp32 vector math is
+# then plain scalar-lane VALU code whatever the optimiser would pick.
+EXTRA_FLAGS = {
+    "attention_decode_gqa.hip": [
+        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
@@ -105,7 +113,7 @@ def build(force: bool = False, verbose: bool = True) -> Path:
         if verbose:
             print(f"[ops.build] hipcc {src}")
         _run([hipcc, "-x", "hip", str(CSRC / src), "-c", "-o", str(obj)]
-             + common_flags)
+             + common_flags + EXTRA_FLAGS.get(src, []))
         objs.append(str(obj))
     # Binding TU: torch headers under hipcc host-compilation.
     torch_flags = [

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "attn_append.h"
+#include "attn_decode_gqa.h"
 #include "attn_launch.h"
 #include "kv_fp8_launch.h"
 
@@ -627,6 +628,101 @@ torch::Tensor attn_decode_qkv_fp8(torch::Tensor qkv, torch::Tensor Kc,
         positions.data_ptr<int>(), kv_lens.data_ptr<int>(),
         slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq, (int)Hkv,
         (float)scale, cur_stream());
+  return O;
+}
+
+// ---- grouped split-KV decode attention (attention_decode_gqa.hip) ----------
+// The checks both cache formats share beyond those of the per-head twins,
+// and the split workspaces: un-normalised O fp32 [n, Hq, splits, 128] and
+// (m, l) fp32 [n, Hq, splits, 2], from the caching allocator, live for the
+// call (stream-ordered reuse afterwards).  Returns rows per split.
+static int check_gqa(const char* op, int64_t B, int64_t Hq, int64_t Hkv,
+                     int64_t S_max, int64_t split_rows) {
+  TORCH_CHECK(Hq / Hkv <= GQA_MAX_GROUP, op, ": group Hq / Hkv = ", Hq / Hkv,
+              " exceeds ", GQA_MAX_GROUP,
+              " (the q heads of a group are one MFMA tile)");
+  TORCH_CHECK(split_rows == -1 ||
+                  (split_rows > 0 && split_rows % 128 == 0 &&
+                   split_rows <= (1 << 24)),
+              op, ": split_rows must be -1 or a positive multiple of 128, got ",
+              split_rows);
+  TORCH_CHECK(B <= 65535 && Hkv <= 65535, op, ": B = ", B, " and Hkv = ", Hkv,
+              " must be at most 65535 (grid y and z)");
+  return gqa_split_rows(S_max, (int)split_rows);
+}
+
+torch::Tensor attn_decode_qkv_gqa(torch::Tensor qkv, torch::Tensor Kc,
+                                  torch::Tensor Vc, torch::Tensor cos_tab,
+                                  torch::Tensor sin_tab,
+                                  torch::Tensor positions,
+                                  torch::Tensor kv_lens,
+                                  torch::Tensor slot_ids, int64_t Hq,
+                                  int64_t Hkv, double scale,
+                                  int64_t split_rows) {
+  const char* op = "attn_decode_qkv_gqa";
+  check_packed_qkv(op, qkv, Hq, Hkv);
+  const int64_t B = qkv.size(0);
+  check_kv_cache(op, Kc, Vc, Hq, Hkv, qkv);
+  const int S_max = (int)Kc.size(1);
+  check_rope_tables(op, cos_tab, sin_tab, S_max, qkv);
+  check_index(op, "positions", positions, B, qkv);
+  check_index(op, "kv_lens", kv_lens, B, qkv);
+  check_index(op, "slot_ids", slot_ids, B, qkv);
+  const int R = check_gqa(op, B, Hq, Hkv, S_max, split_rows);
+  const int64_t splits = (S_max + R - 1) / R;
+  auto O = torch::empty({B, Hq, (int64_t)ATT_D}, qkv.options());
+  if (B == 0) return O;
+  torch::Tensor Ow, MLw;
+  if (splits > 1) {
+    auto f32 = qkv.options().dtype(at::kFloat);
+    Ow = torch::empty({B, Hq, splits, (int64_t)ATT_D}, f32);
+    MLw = torch::empty({B, Hq, splits, 2}, f32);
+  }
+  attn_decode_gqa_launch(
+      qkv.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(),
+      splits > 1 ? Ow.data_ptr() : nullptr,
+      splits > 1 ? MLw.data_ptr() : nullptr, cos_tab.data_ptr(),
+      sin_tab.data_ptr(), positions.data_ptr<int>(), kv_lens.data_ptr<int>(),
+      slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq, (int)Hkv, R,
+      (int)splits, (float)scale, cur_stream());
+  return O;
+}
+
+torch::Tensor attn_decode_qkv_gqa_fp8(torch::Tensor qkv, torch::Tensor Kc,
+                                      torch::Tensor Vc, torch::Tensor Ke,
+                                      torch::Tensor Ve, torch::Tensor cos_tab,
+                                      torch::Tensor sin_tab,
+                                      torch::Tensor positions,
+                                      torch::Tensor kv_lens,
+                                      torch::Tensor slot_ids, int64_t Hq,
+                                      int64_t Hkv, double scale,
+                                      int64_t split_rows) {
+  const char* op = "attn_decode_qkv_gqa_fp8";
+  check_packed_qkv(op, qkv, Hq, Hkv);
+  const int64_t B = qkv.size(0);
+  check_kv_cache_fp8(op, Kc, Vc, Ke, Ve, Hq, Hkv, qkv);
+  const int S_max = (int)Kc.size(1);
+  check_rope_tables(op, cos_tab, sin_tab, S_max, qkv);
+  check_index(op, "positions", positions, B, qkv);
+  check_index(op, "kv_lens", kv_lens, B, qkv);
+  check_index(op, "slot_ids", slot_ids, B, qkv);
+  const int R = check_gqa(op, B, Hq, Hkv, S_max, split_rows);
+  const int64_t splits = (S_max + R - 1) / R;
+  auto O = torch::empty({B, Hq, (int64_t)ATT_D}, qkv.options());
+  if (B == 0) return O;
+  torch::Tensor Ow, MLw;
+  if (splits > 1) {
+    auto f32 = qkv.options().dtype(at::kFloat);
+    Ow = torch::empty({B, Hq, splits, (int64_t)ATT_D}, f32);
+    MLw = torch::empty({B, Hq, splits, 2}, f32);
+  }
+  attn_decode_gqa_fp8_launch(
+      qkv.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), Ke.data_ptr(),
+      Ve.data_ptr(), O.data_ptr(), splits > 1 ? Ow.data_ptr() : nullptr,
+      splits > 1 ? MLw.data_ptr() : nullptr, cos_tab.data_ptr(),
+      sin_tab.data_ptr(), positions.data_ptr<int>(), kv_lens.data_ptr<int>(),
+      slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq, (int)Hkv, R,
+      (int)splits, (float)scale, cur_stream());
   return O;
 }
 
@@ -1262,6 +1358,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_write_fp8", &kv_write_fp8);
   m.def("attn_decode_qkv_fp8", &attn_decode_qkv_fp8);
   m.def("attn_append_fp8", &attn_append_fp8);
+  m.def("attn_decode_qkv_gqa", &attn_decode_qkv_gqa, py::arg("qkv"),
+        py::arg("Kc"), py::arg("Vc"), py::arg("cos"), py::arg("sin"),
+        py::arg("positions"), py::arg("kv_lens"), py::arg("slot_ids"),
+        py::arg("Hq"), py::arg("Hkv"), py::arg("scale"),
+        py::arg("split_rows") = -1);
+  m.def("attn_decode_qkv_gqa_fp8", &attn_decode_qkv_gqa_fp8, py::arg("qkv"),
+        py::arg("Kc"), py::arg("Vc"), py::arg("Ke"), py::arg("Ve"),
+        py::arg("cos"), py::arg("sin"), py::arg("positions"),
+        py::arg("kv_lens"), py::arg("slot_ids"), py::arg("Hq"),
+        py::arg("Hkv"), py::arg("scale"), py::arg("split_rows") = -1);
+  m.attr("DECODE_SPLIT_ROWS") = (int)kDecodeSplitRows;
   m.def("skinny_gemm_fp8_norm", &skinny_gemm_fp8_norm);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

@@ -106,6 +106,9 @@ class TPAttention(nn.Module):
         elif infer_ctx.cache.kv_dtype == "fp8":
             o = self._decode_fp8(q, k, v, infer_ctx).view(
                 B, 1, self.n_q, d)
+        elif infer_ctx.decode_attn == "grouped" and q.is_cuda:
+            o = self._decode_grouped(q, k, v, infer_ctx).view(
+                B, 1, self.n_q, d)
         else:
             infer_ctx.cache.write_decode(self.layer_idx, infer_ctx.slots,
                                          infer_ctx.pos, k, v)
@@ -131,17 +134,42 @@ class TPAttention(nn.Module):
                 q.view(B, self.n_q, d), cache.k[li], cache.v[li],
                 cache.k_exp[li], cache.v_exp[li], infer_ctx.kv_lens,
                 infer_ctx.slot_ids_i32, self.scale)
-        ident = getattr(self, "_rope_ident", None)
-        if ident is None or ident[0].shape[0] < cache.max_seq:
-            ident = (torch.ones(cache.max_seq, d // 2, device=q.device),
-                     torch.zeros(cache.max_seq, d // 2, device=q.device))
-            self._rope_ident = ident
+        ident = _rope_ident(self, cache, q)
         qkv = torch.cat([q.reshape(B, -1), k.reshape(B, -1),
                          v.reshape(B, -1)], -1)
-        return ops.attn_decode_qkv_fp8(
+        fn = (ops.attn_decode_qkv_gqa_fp8
+              if infer_ctx.decode_attn == "grouped"
+              else ops.attn_decode_qkv_fp8)
+        return fn(
             qkv, cache.k[li], cache.v[li], cache.k_exp[li], cache.v_exp[li],
             ident[0], ident[1], infer_ctx.pos.int(), infer_ctx.kv_lens,
             infer_ctx.slot_ids_i32, self.n_q, self.n_kv, self.scale)
+
+    def _decode_grouped(self, q, k, v, infer_ctx):
+        """decode_attn="grouped" over the bf16 cache on the GPU: the
+        grouped kernel writes row p itself, so it takes the roped q and k
+        with the identity rope tables, as _decode_fp8 does."""
+        cache, li = infer_ctx.cache, self.layer_idx
+        B = q.shape[0]
+        ident = _rope_ident(self, cache, q)
+        qkv = torch.cat([q.reshape(B, -1), k.reshape(B, -1),
+                         v.reshape(B, -1)], -1)
+        return ops.attn_decode_qkv_gqa(
+            qkv, cache.k[li], cache.v[li], ident[0], ident[1],
+            infer_ctx.pos.int(), infer_ctx.kv_lens, infer_ctx.slot_ids_i32,
+            self.n_q, self.n_kv, self.scale)
+
+
+def _rope_ident(attn, cache, q):
+    """Identity rope tables (cos 1, sin 0) for the fused decode kernels,
+    built once per attention module."""
+    d = attn.cfg.head_dim
+    ident = getattr(attn, "_rope_ident", None)
+    if ident is None or ident[0].shape[0] < cache.max_seq:
+        ident = (torch.ones(cache.max_seq, d // 2, device=q.device),
+                 torch.zeros(cache.max_seq, d // 2, device=q.device))
+        attn._rope_ident = ident
+    return ident
 
 
 class TPMLP(nn.Module):

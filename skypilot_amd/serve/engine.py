@@ -77,6 +77,11 @@ class InferenceContext:
     # fp8 cache, whole-prompt prefill: (slots, starts, lens) int32 device
     # tensors of the batch's cache write, built by the first layer
     kv_write_idx: Optional[tuple] = None
+    # decode: "per_head" or "grouped" (Engine(decode_attn=...))
+    decode_attn: str = "per_head"
+
+
+DECODE_ATTN = ("per_head", "grouped")
 
 
 @dataclass
@@ -129,7 +134,16 @@ class Engine:
                  tp_rank: int = 0, tp_world: int = 1,
                  prefill_chunk: Optional[int] = None,
                  device_sampling: bool = False,
-                 kv_dtype: str = "bf16", max_logprobs: int = 0):
+                 kv_dtype: str = "bf16", max_logprobs: int = 0,
+                 decode_attn: str = "per_head"):
+        # "grouped" runs decode attention through the grouped split-KV
+        # kernel (docs/KERNELS.md "Grouped split-KV decode"); the default
+        # keeps the per-head kernels and the decode graph as they are.
+        if decode_attn not in DECODE_ATTN:
+            raise ValueError(
+                f"decode_attn must be one of {DECODE_ATTN}, got "
+                f"{decode_attn!r}")
+        self.decode_attn = decode_attn
         # 0 keeps the decode graph and the staged block as they are
         # without the feature; N > 0 adds the log-probability kernel to
         # the graph and lets a request ask for up to N alternatives.
@@ -183,6 +197,11 @@ class Engine:
                                      dtype=dtype)
         self.model.eval()
         self.cfg = getattr(self.model, "cfg_shard", self.model.cfg)
+        group = self.cfg.num_heads // self.cfg.num_kv_heads
+        if decode_attn == "grouped" and group > ops.GQA_MAX_GROUP:
+            raise ValueError(
+                f'decode_attn="grouped" takes at most {ops.GQA_MAX_GROUP} q '
+                f"heads per kv head, the model has {group}")
         self.max_seq = min(max_seq, self.cfg.max_seq_len)
         if max_batch is None:
             if hbm_budget_gb is None:
@@ -557,7 +576,8 @@ class Engine:
                     InferenceContext(
                         cache=self.cache, mode="decode",
                         slots=stg[2].long(), pos=stg[3].long(),
-                        kv_lens=stg[4], slot_ids_i32=stg[5]))
+                        kv_lens=stg[4], slot_ids_i32=stg[5],
+                        decode_attn=self.decode_attn))
 
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
@@ -695,7 +715,8 @@ class Engine:
                                    dtype=torch.int32, device=self.device)
             ctx = InferenceContext(
                 cache=self.cache, mode="decode", slots=slots_t, pos=pos_t,
-                kv_lens=kv_lens, slot_ids_i32=slots_t.int())
+                kv_lens=kv_lens, slot_ids_i32=slots_t.int(),
+                decode_attn=self.decode_attn)
             logits = self.model(toks, positions, ctx)  # [n, 1, V]
         # Device sampling draws the whole batch in one kernel call.  On
         # the host path greedy rows batch into one argmax + one sync and
@@ -865,7 +886,8 @@ class Engine:
                                device=self.device)
         ctx = InferenceContext(cache=self.cache, mode="decode",
                                slots=slots_t, pos=pos_t, kv_lens=kv_lens,
-                               slot_ids_i32=slots_t.int())
+                               slot_ids_i32=slots_t.int(),
+                               decode_attn=self.decode_attn)
         self.model(toks, positions, ctx)
 
     def _loop(self):

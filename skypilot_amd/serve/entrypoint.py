@@ -291,6 +291,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "power-of-two row scales (about half the cache "
                          "bytes: twice the slots or context, half the "
                          "decode-attention traffic)")
+    ap.add_argument("--decode-attn", choices=["per_head", "grouped"],
+                    default="per_head",
+                    help="decode attention kernel: grouped reads each K/V "
+                         "row once per kv head and splits the kv length "
+                         "across blocks (models with at most 16 q heads "
+                         "per kv head)")
     return ap
 
 
@@ -321,6 +327,7 @@ def main():
                         prefill_chunk=args.prefill_chunk,
                         device_sampling=args.device_sampling,
                         kv_dtype=args.kv_dtype,
+                        decode_attn=args.decode_attn,
                         max_logprobs=args.max_logprobs)
         if args.fp8_decode:
             engine.enable_fp8_decode()
@@ -340,6 +347,7 @@ def main():
                     prefill_chunk=args.prefill_chunk,
                     device_sampling=args.device_sampling,
                     kv_dtype=args.kv_dtype,
+                    decode_attn=args.decode_attn,
                         max_logprobs=args.max_logprobs)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode()
