@@ -64,6 +64,9 @@ def main():
     ap.add_argument("--max-batch", type=int, default=64)
     ap.add_argument("--fp8", action="store_true",
                     help="rowwise e4m3fn decode weights")
+    ap.add_argument("--fp8-decode-max-batch", type=int, default=2,
+                    help="with --fp8: largest decode batch served from the "
+                         "fp8 weights (above 2: the fp8 MFMA GEMM)")
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked prefill: tokens per append forward "
                          "(multiple of 64); default whole-prompt prefill")
@@ -96,7 +99,9 @@ def main():
     print(f"kv_dtype={args.kv_dtype} max_batch={eng.max_batch} "
           f"kv_cache_bytes={eng.cache.bytes_needed(eng.cfg, eng.cache.max_batch, eng.max_seq, args.kv_dtype)}")
     if args.fp8:
-        print(f"fp8 decode weights: {eng.enable_fp8_decode()} tensors")
+        n8 = eng.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
+        print(f"fp8 decode weights: {n8} tensors, max batch "
+              f"{args.fp8_decode_max_batch}")
     eng.start()
     prompt = list(range(2, 2 + args.prompt_len))
     # warmup

@@ -617,6 +617,58 @@ def clear_fp8_weights() -> None:
     _FP8_WEIGHTS.clear()
 
 
+def skinny_gemm_fp8_mfma(x: torch.Tensor, w8: torch.Tensor,
+                         scale: torch.Tensor,
+                         row_tiles: int = 0) -> torch.Tensor:
+    """y[n, O] = bf16(scale[o] * sum_k x[n, k] * e4m3(w8[o, k])) for
+    1 <= n <= 64 tokens, I % 128 == 0, O % 16 == 0: the fp8-weight decode
+    GEMM on the matrix cores (skinny_gemm_fp8_mfma.hip).  A token's output
+    bits do not depend on the batch it is computed in, nor on row_tiles
+    (16-row tiles per wave: 0 the measured choice; 1, 2, 4 for the
+    benchmark)."""
+    if x.is_cuda:
+        C = _require_native("skinny_gemm_fp8_mfma")
+        return C.skinny_gemm_fp8_mfma(x, w8, scale, row_tiles)
+    w = w8.view(torch.float8_e4m3fn).float() * scale[:, None]
+    return (x.float() @ w.t()).to(torch.bfloat16)
+
+
+# Largest decode batch that registered fp8 weights serve (opt-in; 2 keeps
+# decode_linear exactly as it was: the fp8 GEMV for n <= 2 only).
+_FP8_MAX_BATCH = 2
+
+
+def set_fp8_decode_max_batch(m: int) -> None:
+    """Let registered fp8 weights serve decode batches of 3..m tokens
+    through skinny_gemm_fp8_mfma, where the measured route table says it
+    wins.  m in 2..64; 2, the default, turns it off."""
+    global _FP8_MAX_BATCH
+    if not isinstance(m, int) or isinstance(m, bool) or not 2 <= m <= 64:
+        raise ValueError(
+            f"set_fp8_decode_max_batch: m must be an int in 2..64, got {m!r}")
+    _FP8_MAX_BATCH = m
+
+
+# Measured routes for 3 <= n <= _FP8_MAX_BATCH (bench_gemm_fp8_mfma.py on
+# MI355X, docs/BENCHMARKS.md "FP8-weight MFMA decode GEMM"): per shape
+# class, the column-tile counts NT = ceil(n/16) at which the fp8 MFMA
+# kernel beat the path decode_linear otherwise takes by more than the
+# spread of the repeats.  "wide" is O >= 16384 (four row tiles per wave),
+# "deep" I > 8192, "square" the rest.  Wide wins at every n (1.9x at 16
+# down to 1.03x-1.09x at 64), square up to n = 32 (1.05x-1.08x there; 0.88x-
+# 0.97x at 48), deep up to n = 16 (1.07x; 0.90x at 32).  Where it loses, the
+# X fragments every block re-reads from L2 bound it, not the W stream.
+_FP8_MFMA_ROUTES = {
+    "wide": (1, 2, 3, 4),
+    "deep": (1,),
+    "square": (1, 2),
+}
+
+
+def _fp8_mfma_class(i: int, o: int) -> str:
+    return "wide" if o >= 16384 else "deep" if i > 8192 else "square"
+
+
 def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     """F.linear for the decode step: y = x @ W^T with x [.., n, in],
     n <= 8.  On GPU this runs the weight-bandwidth-bound skinny GEMV
@@ -640,12 +692,22 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     # the bf16 multirow GEMV amortizes the weight stream and fp8's
     # unpack VALU cost dominates (measured: @8 streams 1521 -> 1069
     # tok/s with fp8 everywhere).
-    if (x.is_cuda and x.dtype == torch.bfloat16 and 1 <= n <= 2
-            and i % 1024 == 0 and _FP8_WEIGHTS):
+    # From n = 3 up the fp8 weights are served by the MFMA kernel, whose
+    # per-weight VALU work does not grow with n: opt-in
+    # (set_fp8_decode_max_batch) and only where _FP8_MFMA_ROUTES has it
+    # winning.
+    mfma = (3 <= n <= _FP8_MAX_BATCH and i % 128 == 0 and o % 16 == 0
+            and (n + 15) // 16 in _FP8_MFMA_ROUTES[_fp8_mfma_class(i, o)])
+    if (x.is_cuda and x.dtype == torch.bfloat16 and _FP8_WEIGHTS
+            and ((1 <= n <= 2 and i % 1024 == 0) or mfma)):
         ent = _FP8_WEIGHTS.get(weight.data_ptr())
         # data_ptr can be recycled after a free; require matching shape
         if ent is not None and tuple(ent[0].shape) != tuple(weight.shape):
             ent = None
+        if ent is not None and mfma:
+            y = skinny_gemm_fp8_mfma(x.reshape(n, i).contiguous(), ent[0],
+                                     ent[1])
+            return y.view(*lead, o)
         if ent is not None:
             C = _require_native("skinny_gemm_fp8")
             y = C.skinny_gemm_fp8(x.reshape(n, i).contiguous(), ent[0],
@@ -1092,4 +1154,5 @@ __all__ = [
     "kv_quantize", "kv_dequantize", "kv_write_fp8", "attn_decode_qkv_fp8",
     "attn_append_fp8", "attn_decode_fp8",
     "attn_decode_qkv_gqa", "attn_decode_qkv_gqa_fp8",
+    "skinny_gemm_fp8_mfma", "set_fp8_decode_max_batch",
 ]

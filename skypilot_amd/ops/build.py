@@ -34,18 +34,21 @@ HIP_SOURCES = [
     "kv_write_fp8.hip",
     "swiglu.hip",
     "skinny_gemm.hip",
+    "skinny_gemm_fp8_mfma.hip",
     "wgrad_gemm.hip",
     "decode_fused.hip",
     "decode_sample.hip",
     "mfma_probe.hip",
 ]
 CPP_SOURCES = ["bindings.cpp"]
-# Extra flags per device TU.  The grouped decode kernel is built without
-# packed-fp32 instructions (v_pk_mul_f32 and kin): its fp32 vector math is
-# then plain scalar-lane VALU code whatever the optimiser would pick.
+# Extra flags per device TU.  The grouped decode kernel and the fp8 MFMA
+# decode GEMM are built without packed-fp32 instructions (v_pk_mul_f32 and
+# kin): their fp32 vector math is then plain scalar-lane VALU code whatever
+# the optimiser would pick.
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
-    "attention_decode_gqa.hip": [
-        "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "attention_decode_gqa.hip": _NO_PK_F32,
+    "skinny_gemm_fp8_mfma.hip": _NO_PK_F32,
 }
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

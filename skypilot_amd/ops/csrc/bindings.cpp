@@ -48,6 +48,8 @@ void skinny_gemm_swiglu_launch(const void*, const void*, void*, int, int,
 void transpose_bf16_launch(const void*, void*, int, int, hipStream_t);
 void skinny_gemm_fp8_launch(const void*, const float*, const void*, void*,
                             int, int, int, hipStream_t);
+void skinny_gemm_fp8_mfma_launch(const void*, const float*, const void*,
+                                 void*, int, int, int, int, hipStream_t);
 void gemm_nt_launch(const void*, const void*, void*, int, int, long long,
                     hipStream_t);
 void adamw_mt_launch(const void*, const void*, const void*, const void*,
@@ -999,6 +1001,37 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor X, torch::Tensor W8,
   return y;
 }
 
+torch::Tensor skinny_gemm_fp8_mfma(torch::Tensor X, torch::Tensor W8,
+                                   torch::Tensor scale, int64_t row_tiles) {
+  // Same product as skinny_gemm_fp8 on the matrix cores, N up to 64
+  // (skinny_gemm_fp8_mfma.hip).  row_tiles: 0 = the measured choice; 1, 2
+  // or 4 force the row tiles per wave (same bits; for the benchmark).
+  const char* op = "skinny_gemm_fp8_mfma";
+  TORCH_CHECK(row_tiles == 0 || row_tiles == 1 || row_tiles == 2 ||
+                  row_tiles == 4,
+              op, ": row_tiles must be 0, 1, 2 or 4, got ", row_tiles);
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(N >= 1 && N <= 64, op, ": N must be 1..64, got ", N);
+  TORCH_CHECK(I >= 128 && I % 128 == 0 &&
+                  I <= std::numeric_limits<int>::max(),
+              op, ": I must be a positive multiple of 128, got ", I);
+  check_fp8_weight(op, W8, scale, I, X);
+  const int64_t O = W8.size(0);
+  TORCH_CHECK(O % 16 == 0, op, ": O must be a multiple of 16, got ", O);
+  auto y = torch::empty({N, O}, X.options());
+  const torch::Tensor* ts[] = {&X, &W8, &scale, &y};
+  const char* names[] = {"X", "W8", "scale", "the output"};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(aligned16(*ts[i]), op, ": ", names[i],
+                " must start on a 16-byte boundary");
+  skinny_gemm_fp8_mfma_launch(W8.data_ptr(), scale.data_ptr<float>(),
+                              X.data_ptr(), y.data_ptr(), (int)N, (int)I,
+                              (int)O, (int)row_tiles, cur_stream());
+  return y;
+}
+
 torch::Tensor skinny_gemm(torch::Tensor X, torch::Tensor W) {
   // Y[N,O] = X[N,I] @ W[O,I]^T (decode GEMV; see skinny_gemm.hip)
   CHECK_GPU(X); CHECK_CONTIG(X); CHECK_BF16(X);
@@ -1337,6 +1370,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_append", &attn_append);
   m.def("skinny_gemm", &skinny_gemm);
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8);
+  m.def("skinny_gemm_fp8_mfma", &skinny_gemm_fp8_mfma, py::arg("x"),
+        py::arg("w8"), py::arg("scale"), py::arg("row_tiles") = 0);
   m.def("transpose_bf16", &transpose_bf16);
   m.def("gemm_nt", &gemm_nt);
   m.def("wgrad_tn", &wgrad_tn);

@@ -241,12 +241,17 @@ class Engine:
             self._scratch_slot = self.free_slots.pop()
             self.max_batch -= 1
 
-    def enable_fp8_decode(self, min_bytes: int = 1 << 20) -> int:
+    def enable_fp8_decode(self, min_bytes: int = 1 << 20,
+                          max_batch: int = 2) -> int:
         """Quantize every large linear weight to row-wise e4m3fn and
         route the decode GEMVs through the fp8 kernel (half the streamed
         bytes on the weight-bandwidth-bound decode path; prefill stays
-        bf16).  Returns the number of weights registered."""
+        bf16).  max_batch (2..64) is the largest decode batch the fp8
+        weights serve: above 2 the batched steps run the fp8 MFMA GEMM
+        (ops.set_fp8_decode_max_batch).  Returns the number of weights
+        registered."""
         from skypilot_amd import ops as _ops
+        _ops.set_fp8_decode_max_batch(max_batch)
         n = 0
         for name, p in self.model.named_parameters():
             if (p.ndim == 2 and p.dtype == torch.bfloat16

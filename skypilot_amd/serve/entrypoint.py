@@ -283,6 +283,10 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fp8-decode", action="store_true",
                     help="quantize weights to rowwise e4m3fn for the "
                          "decode GEMVs (~2x single-stream decode)")
+    ap.add_argument("--fp8-decode-max-batch", type=int, default=2,
+                    help="with --fp8-decode: largest decode batch served "
+                         "from the fp8 weights (2..64); above 2 batched "
+                         "steps run the fp8 MFMA GEMM")
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree; run under torchrun "
                          "with one rank per GPU (70B serving: --tp 8)")
@@ -330,7 +334,7 @@ def main():
                         decode_attn=args.decode_attn,
                         max_logprobs=args.max_logprobs)
         if args.fp8_decode:
-            engine.enable_fp8_decode()
+            engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         if rank > 0:
             engine.follower_loop()
             return
@@ -350,7 +354,7 @@ def main():
                     decode_attn=args.decode_attn,
                         max_logprobs=args.max_logprobs)
     if args.fp8_decode:
-        n8 = engine.enable_fp8_decode()
+        n8 = engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
     engine.start()
     app = create_app(engine, args.model)
