@@ -67,6 +67,8 @@ def main():
     ap.add_argument("--fp8-decode-max-batch", type=int, default=2,
                     help="with --fp8: largest decode batch served from the "
                          "fp8 weights (above 2: the fp8 MFMA GEMM)")
+    ap.add_argument("--fp4", action="store_true",
+                    help="MXFP4 decode weights (not together with --fp8)")
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked prefill: tokens per append forward "
                          "(multiple of 64); default whole-prompt prefill")
@@ -102,6 +104,8 @@ def main():
         n8 = eng.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         print(f"fp8 decode weights: {n8} tensors, max batch "
               f"{args.fp8_decode_max_batch}")
+    if args.fp4:
+        print(f"fp4 decode weights: {eng.enable_fp4_decode()} tensors")
     eng.start()
     prompt = list(range(2, 2 + args.prompt_len))
     # warmup

@@ -669,6 +669,130 @@ def _fp8_mfma_class(i: int, o: int) -> str:
     return "wide" if o >= 16384 else "deep" if i > 8192 else "square"
 
 
+# ---- MXFP4 decode weights (docs/KERNELS.md "MXFP4-weight MFMA decode GEMM")
+# OCP MXFP4: e2m1 codes in blocks of 32 along K with one E8M0 exponent byte
+# per block, 4.25 bits per weight.  The two functions below are the
+# definition, in plain torch with integer bit arithmetic.  Byte j of a row
+# holds element 2j in bits 0..3 and element 2j+1 in bits 4..7; a code is the
+# sign in bit 3 and an index in bits 0..2 into _E2M1_GRID.
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# Midpoints between neighbouring grid values.  A tie goes to the even code:
+# down where the lower index is even (x > mid moves up), up where it is odd.
+_E2M1_MIDS = ((0.25, False), (0.75, True), (1.25, False), (1.75, True),
+              (2.5, False), (3.5, True), (5.0, False))
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """w [O, I], I % 32 == 0 -> (codes uint8 [O, I/2], exps uint8
+    [O, I/32]).  Per block of 32 consecutive k of a row, with amax = max
+    |w| in fp32: n is the smallest integer with amax <= 6 * 2^n, clamped to
+    [-100, 100] (0 for amax == 0), the exponent byte is n + 127 and code =
+    e2m1(w * 2^-n), round to nearest, ties to the even code.  Nothing
+    saturates (this is kv_quantize's rule, not floor(log2 amax) - 2).
+    Blocks holding NaN or Inf give unspecified contents."""
+    O, I = w.shape
+    if I % 32:
+        raise ValueError(f"quantize_mxfp4: I must be a multiple of 32, got {I}")
+    xf = w.detach().float().reshape(O, I // 32, 32)
+    amax = xf.abs().amax(-1)
+    u = amax.contiguous().view(torch.int32) & 0x7FFFFFFF
+    # 6 = 1.5 * 2^2, and 0x400000 is the fp32 mantissa of 1.5
+    n = (u >> 23) - 129 + ((u & 0x7FFFFF) > 0x400000).to(torch.int32)
+    n = n.clamp(-100, 100)
+    n = torch.where(u == 0, torch.zeros_like(n), n)
+    inv = ((127 - n) << 23).view(torch.float32)      # 2^-n, exact
+    a = (xf * inv.unsqueeze(-1)).abs()
+    idx = torch.zeros_like(a, dtype=torch.uint8)
+    for mid, up in _E2M1_MIDS:
+        idx += (a >= mid) if up else (a > mid)
+    c = (idx | (torch.signbit(xf).to(torch.uint8) << 3)).reshape(O, I // 2, 2)
+    codes = c[..., 0] | (c[..., 1] << 4)
+    return codes.contiguous(), (n + 127).to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes: torch.Tensor, exps: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [O, I/2], exps uint8 [O, I/32] -> fp32 [O, I]:
+    e2m1(code) * 2^(exp - 127), every value exact in bf16."""
+    O = codes.shape[0]
+    c = torch.stack([codes & 15, codes >> 4], dim=-1).reshape(O, -1).long()
+    grid = torch.tensor(_E2M1_GRID, dtype=torch.float32, device=codes.device)
+    v = torch.where((c & 8) != 0, -grid[c & 7], grid[c & 7])
+    scale = (exps.to(torch.int32) << 23).view(torch.float32)
+    return (v.reshape(O, -1, 32) * scale.unsqueeze(-1)).reshape(O, -1)
+
+
+def skinny_gemm_fp4_mfma(x: torch.Tensor, codes: torch.Tensor,
+                         exps: torch.Tensor,
+                         row_tiles: int = 0) -> torch.Tensor:
+    """y[n, O] = bf16(sum_k x[n, k] * dequantize_mxfp4(codes, exps)[o, k])
+    for 1 <= n <= 64 tokens, I % 128 == 0, O % 16 == 0: the MXFP4-weight
+    decode GEMM on the matrix cores (skinny_gemm_fp4_mfma.hip), fp32
+    accumulation.  Exponent bytes in [27, 227].  A token's output bits do
+    not depend on the batch it is computed in, nor on row_tiles (16-row
+    tiles per wave: 0 the measured choice; 1, 2, 4 for the benchmark)."""
+    if x.is_cuda:
+        C = _require_native("skinny_gemm_fp4_mfma")
+        return C.skinny_gemm_fp4_mfma(x, codes, exps, row_tiles)
+    return (x.float() @ dequantize_mxfp4(codes, exps).t()).to(torch.bfloat16)
+
+
+_FP4_WEIGHTS: dict = {}
+# Largest decode batch that registered fp4 weights serve.
+_FP4_MAX_BATCH = 64
+
+
+def register_fp4_weight(w: torch.Tensor) -> None:
+    """Quantize a bf16 [O, I] weight to MXFP4 and register it for decode
+    routing through skinny_gemm_fp4_mfma."""
+    _FP4_WEIGHTS[w.data_ptr()] = quantize_mxfp4(w)
+
+
+def clear_fp4_weights() -> None:
+    _FP4_WEIGHTS.clear()
+
+
+def set_fp4_decode_max_batch(m: int) -> None:
+    """Registered fp4 weights serve decode batches of 1..m tokens through
+    skinny_gemm_fp4_mfma, where the measured route table says it wins.
+    m in 1..64; 64 is the default."""
+    global _FP4_MAX_BATCH
+    if not isinstance(m, int) or isinstance(m, bool) or not 1 <= m <= 64:
+        raise ValueError(
+            f"set_fp4_decode_max_batch: m must be an int in 1..64, got {m!r}")
+    _FP4_MAX_BATCH = m
+
+
+# Measured routes for 1 <= n <= _FP4_MAX_BATCH (bench_gemm_fp4_mfma.py on
+# MI355X, docs/BENCHMARKS.md "MXFP4-weight MFMA decode GEMM"): per shape
+# class (_fp8_mfma_class), the column-tile counts NT = ceil(n/16) at which
+# the fp4 MFMA kernel beat what decode_linear runs with bf16 weights on
+# every measured shape of the class by more than the spread of the repeats
+# (under 1 % but for n = 1 on the vocabulary projection, 3 %).  "wide" wins
+# up to n = 48 (1.3x-2.2x at n <= 16, 1.07x-1.24x at 48; 0.92x at 64).
+# "square" wins at n = 32 (1.06x-1.10x) and at 4..16 on both shapes, but NT =
+# 1 is not routed because n = 1 loses (0.68x-0.86x); "deep" loses at every n
+# (0.57x-0.91x).  Where it loses at small n the kernel is latency-bound (one
+# chunk of W in flight per wave), at large n X-bound.
+_FP4_MFMA_ROUTES = {
+    "wide": (1, 2, 3),
+    "deep": (),
+    "square": (2,),
+}
+
+
+def _decode_linear_fp4(x, weight, n, i, o):
+    """The fp4 route of decode_linear, or None where it does not apply."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16
+            and 1 <= n <= _FP4_MAX_BATCH and i % 128 == 0 and o % 16 == 0
+            and (n + 15) // 16 in _FP4_MFMA_ROUTES[_fp8_mfma_class(i, o)]):
+        return None
+    ent = _FP4_WEIGHTS.get(weight.data_ptr())
+    # data_ptr can be recycled after a free; require matching shape
+    if ent is None or tuple(ent[0].shape) != (o, i // 2):
+        return None
+    return skinny_gemm_fp4_mfma(x.reshape(n, i).contiguous(), ent[0], ent[1])
+
+
 def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     """F.linear for the decode step: y = x @ W^T with x [.., n, in],
     n <= 8.  On GPU this runs the weight-bandwidth-bound skinny GEMV
@@ -680,6 +804,12 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     for d in lead:
         n *= d
     i, o = x.shape[-1], weight.shape[0]
+    # Weights registered as MXFP4 come first; with none registered nothing
+    # below changes.
+    if _FP4_WEIGHTS:
+        y = _decode_linear_fp4(x, weight, n, i, o)
+        if y is not None:
+            return y.view(*lead, o)
     wbytes = 2 * i * o
     # Measured routing (bench_gemv.py on MI355X, docs/BENCHMARKS.md):
     # n=1 always wins (W streams at 6.5-7.3 TB/s; hipBLASLt floors at
@@ -1155,4 +1285,6 @@ __all__ = [
     "attn_append_fp8", "attn_decode_fp8",
     "attn_decode_qkv_gqa", "attn_decode_qkv_gqa_fp8",
     "skinny_gemm_fp8_mfma", "set_fp8_decode_max_batch",
+    "quantize_mxfp4", "dequantize_mxfp4", "skinny_gemm_fp4_mfma",
+    "register_fp4_weight", "clear_fp4_weights", "set_fp4_decode_max_batch",
 ]

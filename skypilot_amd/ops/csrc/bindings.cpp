@@ -50,6 +50,8 @@ void skinny_gemm_fp8_launch(const void*, const float*, const void*, void*,
                             int, int, int, hipStream_t);
 void skinny_gemm_fp8_mfma_launch(const void*, const float*, const void*,
                                  void*, int, int, int, int, hipStream_t);
+void skinny_gemm_fp4_mfma_launch(const void*, const void*, const void*,
+                                 void*, int, int, int, int, hipStream_t);
 void gemm_nt_launch(const void*, const void*, void*, int, int, long long,
                     hipStream_t);
 void adamw_mt_launch(const void*, const void*, const void*, const void*,
@@ -1032,6 +1034,47 @@ torch::Tensor skinny_gemm_fp8_mfma(torch::Tensor X, torch::Tensor W8,
   return y;
 }
 
+torch::Tensor skinny_gemm_fp4_mfma(torch::Tensor X, torch::Tensor codes,
+                                   torch::Tensor exps, int64_t row_tiles) {
+  // Y[N,O] = X[N,I] @ W^T over MXFP4 weights (skinny_gemm_fp4_mfma.hip):
+  // codes uint8 [O, I/2], two e2m1 nibbles per byte; exps uint8 [O, I/32],
+  // one E8M0 byte per block of 32 k.  row_tiles: 0 = the measured choice;
+  // 1, 2 or 4 force the row tiles per wave (same bits; for the benchmark).
+  const char* op = "skinny_gemm_fp4_mfma";
+  TORCH_CHECK(row_tiles == 0 || row_tiles == 1 || row_tiles == 2 ||
+                  row_tiles == 4,
+              op, ": row_tiles must be 0, 1, 2 or 4, got ", row_tiles);
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(N >= 1 && N <= 64, op, ": N must be 1..64, got ", N);
+  TORCH_CHECK(I >= 128 && I % 128 == 0 &&
+                  I <= std::numeric_limits<int>::max(),
+              op, ": I must be a positive multiple of 128, got ", I);
+  check_dense(op, "codes", codes, at::kByte, X);
+  TORCH_CHECK(codes.dim() == 2 && codes.size(1) == I / 2, op,
+              ": codes must be [O, I/2] with I/2 = ", I / 2, ", got ",
+              codes.sizes());
+  const int64_t O = codes.size(0);
+  TORCH_CHECK(O >= 16 && O % 16 == 0 &&
+                  O <= std::numeric_limits<int>::max(),
+              op, ": O must be a positive multiple of 16, got ", O);
+  check_dense(op, "exps", exps, at::kByte, X);
+  TORCH_CHECK(exps.dim() == 2 && exps.size(0) == O && exps.size(1) == I / 32,
+              op, ": exps must be [O, I/32] = [", O, ", ", I / 32, "], got ",
+              exps.sizes());
+  auto y = torch::empty({N, O}, X.options());
+  const torch::Tensor* ts[] = {&X, &codes, &exps, &y};
+  const char* names[] = {"X", "codes", "exps", "the output"};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(aligned16(*ts[i]), op, ": ", names[i],
+                " must start on a 16-byte boundary");
+  skinny_gemm_fp4_mfma_launch(codes.data_ptr(), exps.data_ptr(), X.data_ptr(),
+                              y.data_ptr(), (int)N, (int)I, (int)O,
+                              (int)row_tiles, cur_stream());
+  return y;
+}
+
 torch::Tensor skinny_gemm(torch::Tensor X, torch::Tensor W) {
   // Y[N,O] = X[N,I] @ W[O,I]^T (decode GEMV; see skinny_gemm.hip)
   CHECK_GPU(X); CHECK_CONTIG(X); CHECK_BF16(X);
@@ -1372,6 +1415,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8);
   m.def("skinny_gemm_fp8_mfma", &skinny_gemm_fp8_mfma, py::arg("x"),
         py::arg("w8"), py::arg("scale"), py::arg("row_tiles") = 0);
+  m.def("skinny_gemm_fp4_mfma", &skinny_gemm_fp4_mfma, py::arg("x"),
+        py::arg("codes"), py::arg("exps"), py::arg("row_tiles") = 0);
   m.def("transpose_bf16", &transpose_bf16);
   m.def("gemm_nt", &gemm_nt);
   m.def("wgrad_tn", &wgrad_tn);

@@ -251,14 +251,43 @@ class Engine:
         (ops.set_fp8_decode_max_batch).  Returns the number of weights
         registered."""
         from skypilot_amd import ops as _ops
+        self._claim_decode_weights("fp8")
         _ops.set_fp8_decode_max_batch(max_batch)
+        return self._register_decode_weights(_ops.register_fp8_weight,
+                                             min_bytes, 1024)
+
+    def enable_fp4_decode(self, min_bytes: int = 1 << 20,
+                          max_batch: int = 64) -> int:
+        """Quantize every large linear weight to MXFP4 (ops.quantize_mxfp4,
+        4.25 bits per weight) and route decode batches of 1..max_batch
+        tokens through the fp4 MFMA GEMM where its measured table has it
+        winning (ops.set_fp4_decode_max_batch); prefill stays bf16.  The
+        weights are the ones enable_fp8_decode takes, with I % 128 == 0.
+        One engine serves fp8 or fp4 decode weights, not both.  Returns the
+        number of weights registered."""
+        from skypilot_amd import ops as _ops
+        self._claim_decode_weights("fp4")
+        _ops.set_fp4_decode_max_batch(max_batch)
+        return self._register_decode_weights(_ops.register_fp4_weight,
+                                             min_bytes, 128)
+
+    def _claim_decode_weights(self, fmt: str) -> None:
+        have = getattr(self, "_decode_weight_format", fmt)
+        if have != fmt:
+            raise ValueError(
+                f"enable_{fmt}_decode: this engine already serves {have} "
+                f"decode weights")
+        self._decode_weight_format = fmt
+
+    def _register_decode_weights(self, register, min_bytes: int,
+                                 k_multiple: int) -> int:
         n = 0
         for name, p in self.model.named_parameters():
             if (p.ndim == 2 and p.dtype == torch.bfloat16
                     and p.numel() * 2 >= min_bytes
-                    and p.shape[1] % 1024 == 0
+                    and p.shape[1] % k_multiple == 0
                     and "embed" not in name):
-                _ops.register_fp8_weight(p.data)
+                register(p.data)
                 n += 1
         # The decode path lazily packs [q|k|v] into a single GEMV weight
         # (models/llama.py _wqkv) that is NOT a named parameter —
@@ -272,8 +301,8 @@ class Engine:
                 a._wqkv = torch.cat(
                     [a.wq.weight, a.wk.weight, a.wv.weight], dim=0)
             if (getattr(a, "_wqkv", None) is not None
-                    and a._wqkv.shape[1] % 1024 == 0):
-                _ops.register_fp8_weight(a._wqkv)
+                    and a._wqkv.shape[1] % k_multiple == 0):
+                register(a._wqkv)
                 n += 1
         return n
 

@@ -287,6 +287,13 @@ def build_parser() -> argparse.ArgumentParser:
                     help="with --fp8-decode: largest decode batch served "
                          "from the fp8 weights (2..64); above 2 batched "
                          "steps run the fp8 MFMA GEMM")
+    ap.add_argument("--fp4-decode", action="store_true",
+                    help="quantize weights to MXFP4 (e2m1 codes, one "
+                         "exponent byte per 32 k) for the decode GEMMs; "
+                         "not together with --fp8-decode")
+    ap.add_argument("--fp4-decode-max-batch", type=int, default=64,
+                    help="with --fp4-decode: largest decode batch served "
+                         "from the fp4 weights (1..64)")
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree; run under torchrun "
                          "with one rank per GPU (70B serving: --tp 8)")
@@ -335,6 +342,8 @@ def main():
                         max_logprobs=args.max_logprobs)
         if args.fp8_decode:
             engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
+        if args.fp4_decode:
+            engine.enable_fp4_decode(max_batch=args.fp4_decode_max_batch)
         if rank > 0:
             engine.follower_loop()
             return
@@ -356,6 +365,9 @@ def main():
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
+    if args.fp4_decode:
+        n4 = engine.enable_fp4_decode(max_batch=args.fp4_decode_max_batch)
+        print(f"fp4 decode weights: {n4} tensors quantized", flush=True)
     engine.start()
     app = create_app(engine, args.model)
     print(f"serving {args.model} on {args.host}:{args.port} "
