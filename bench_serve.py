@@ -69,6 +69,9 @@ def main():
                          "fp8 weights (above 2: the fp8 MFMA GEMM)")
     ap.add_argument("--fp4", action="store_true",
                     help="MXFP4 decode weights (not together with --fp8)")
+    ap.add_argument("--fp4-prefill", type=int, default=None, metavar="N",
+                    help="MXFP4 weights for prefill too, from N tokens up "
+                         "(0: the measured thresholds)")
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked prefill: tokens per append forward "
                          "(multiple of 64); default whole-prompt prefill")
@@ -106,6 +109,10 @@ def main():
               f"{args.fp8_decode_max_batch}")
     if args.fp4:
         print(f"fp4 decode weights: {eng.enable_fp4_decode()} tensors")
+    if args.fp4_prefill is not None:
+        n4 = eng.enable_fp4_prefill(args.fp4_prefill or "measured")
+        print(f"fp4 prefill weights: {n4} tensors, from "
+              f"{args.fp4_prefill or 'measured'} tokens")
     eng.start()
     prompt = list(range(2, 2 + args.prompt_len))
     # warmup

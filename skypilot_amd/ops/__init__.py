@@ -348,6 +348,10 @@ def linear(x, w, b=None, route: int = -1):
     if not (x.is_cuda and x.dtype == torch.bfloat16
             and w.dtype == torch.bfloat16):
         return torch.nn.functional.linear(x, w, b)
+    if _FP4_PREFILL is not None and not torch.is_grad_enabled():
+        y = _prefill_linear_fp4(x, w, b)
+        if y is not None:
+            return y
     _require_native("linear")
     return _LinearFn.apply(x, w, b, route)
 
@@ -392,6 +396,10 @@ def qkv_linear(x, wq, wk, wv, bq=None, bk=None, bv=None, route: int = -1):
     if not (x.is_cuda and x.dtype == torch.bfloat16
             and wq.dtype == torch.bfloat16):
         return lin(x, wq, bq), lin(x, wk, bk), lin(x, wv, bv)
+    if _FP4_PREFILL is not None and not torch.is_grad_enabled():
+        # three calls; a projection the route does not take is F.linear's
+        return tuple(linear(x, w, b, route)
+                     for w, b in ((wq, bq), (wk, bk), (wv, bv)))
     _require_native("qkv_linear")
     return _QKVLinearFn.apply(x, wq, wk, wv, bq, bk, bv, route)
 
@@ -791,6 +799,124 @@ def _decode_linear_fp4(x, weight, n, i, o):
     if ent is None or tuple(ent[0].shape) != (o, i // 2):
         return None
     return skinny_gemm_fp4_mfma(x.reshape(n, i).contiguous(), ent[0], ent[1])
+
+
+# ---- MXFP4 x MXFP8 prefill GEMM (docs/KERNELS.md "MXFP4 x MXFP8 prefill
+# GEMM").  Activations in OCP MXFP8: e4m3fn codes in blocks of 32 along K
+# with one E8M0 exponent byte per block, by the rule of kv_quantize and
+# quantize_mxfp4.  The two functions below are the definition, in plain torch
+# with integer bit arithmetic; quantize_mxfp8_rows_kernel reproduces them bit
+# for bit.
+_FP4_PREFILL_TILE = 128     # the GEMM's token tile
+
+
+def quantize_mxfp8(x: torch.Tensor):
+    """x [n, I], I % 32 == 0 -> (codes uint8 [n, I], exps uint8 [n, I/32]).
+    Per block of 32 consecutive k of a row, with amax = max |x| in fp32: n is
+    the smallest integer with amax <= 448 * 2^n, clamped to [-100, 100] (0
+    for amax == 0), the exponent byte is n + 127 and code = e4m3fn(x * 2^-n),
+    round to nearest even.  Nothing saturates.  Blocks holding NaN or Inf
+    give unspecified contents."""
+    N, I = x.shape
+    if I % 32:
+        raise ValueError(f"quantize_mxfp8: I must be a multiple of 32, got {I}")
+    xf = x.detach().float().reshape(N, I // 32, 32)
+    amax = xf.abs().amax(-1)
+    u = amax.contiguous().view(torch.int32) & 0x7FFFFFFF
+    # 448 = 1.75 * 2^8, and 0x600000 is the fp32 mantissa of 1.75
+    n = (u >> 23) - 135 + ((u & 0x7FFFFF) > 0x600000).to(torch.int32)
+    n = n.clamp(-100, 100)
+    n = torch.where(u == 0, torch.zeros_like(n), n)
+    inv = ((127 - n) << 23).view(torch.float32)      # 2^-n, exact
+    codes = (xf * inv.unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    return (codes.reshape(N, I).contiguous(),
+            (n + 127).to(torch.uint8).contiguous())
+
+
+def dequantize_mxfp8(codes: torch.Tensor, exps: torch.Tensor) -> torch.Tensor:
+    """codes uint8 [n, I], exps uint8 [n, I/32] -> fp32 [n, I]:
+    e4m3fn(code) * 2^(exp - 127), every value exact."""
+    N = codes.shape[0]
+    scale = (exps.to(torch.int32) << 23).view(torch.float32)
+    v = codes.view(torch.float8_e4m3fn).float().reshape(N, -1, 32)
+    return (v * scale.unsqueeze(-1)).reshape(N, -1)
+
+
+def quantize_mxfp8_rows(x: torch.Tensor):
+    """quantize_mxfp8 as the GEMM takes it: rows padded to a multiple of the
+    token tile (128) with zero codes and exponent 127.  On the GPU this is
+    quantize_mxfp8_rows_kernel (bf16 x, 16-byte aligned)."""
+    if x.is_cuda:
+        return _require_native("quantize_mxfp8_rows").quantize_mxfp8_rows(x)
+    codes, exps = quantize_mxfp8(x)
+    pad = -x.shape[0] % _FP4_PREFILL_TILE
+    return (torch.nn.functional.pad(codes, (0, 0, 0, pad)),
+            torch.nn.functional.pad(exps, (0, 0, 0, pad), value=127))
+
+
+def gemm_mxfp4_a8(x: torch.Tensor, codes: torch.Tensor,
+                  exps: torch.Tensor) -> torch.Tensor:
+    """y[n, O] = bf16(sum_k dequantize_mxfp8(*quantize_mxfp8(x))[n, k] *
+    dequantize_mxfp4(codes, exps)[o, k]) for any n >= 1, I % 128 == 0 and
+    O % 128 == 0: x is quantised to MXFP8 and contracted with the MXFP4
+    weights on the block-scaled matrix instruction (gemm_mxfp4_a8.hip), fp32
+    accumulation in an order that depends on I alone, so a token's output
+    bits do not depend on the batch it is computed in."""
+    if x.is_cuda:
+        return _require_native("gemm_mxfp4_a8").gemm_mxfp4_a8(x, codes, exps)
+    xd = dequantize_mxfp8(*quantize_mxfp8(x))
+    return (xd @ dequantize_mxfp4(codes, exps).t()).to(torch.bfloat16)
+
+
+# Smallest token count that ops.linear / ops.qkv_linear serve from registered
+# fp4 weights: None is off, an int one threshold for every shape, "measured"
+# the table below.
+_FP4_PREFILL = None
+
+# Measured thresholds per shape class (_fp8_mfma_class), from
+# bench_gemm_fp4_prefill.py on MI355X (docs/BENCHMARKS.md "MXFP4 x MXFP8
+# prefill GEMM"): the smallest measured token count from which quantiser plus
+# GEMM beat F.linear on the bf16 weight by more than the spread, there and at
+# every larger measured count.  A class that never won is absent and is not
+# routed under "measured".  Empty: at 128..8192 tokens the kernel ran at
+# 0.33x-0.67x of F.linear on all four llama3-8b projections, so it is reached
+# through an explicit min_tokens only.
+_FP4_PREFILL_ROUTES: dict = {}
+
+
+def set_fp4_prefill(min_tokens) -> None:
+    """Route ops.linear and ops.qkv_linear through gemm_mxfp4_a8 for weights
+    registered as MXFP4, from min_tokens tokens up, when autograd is off.
+    None (the default) turns the route off, an int >= 1 forces it from that
+    count, "measured" takes the per-class thresholds of _FP4_PREFILL_ROUTES."""
+    global _FP4_PREFILL
+    ok = (min_tokens is None or min_tokens == "measured"
+          or (isinstance(min_tokens, int) and not isinstance(min_tokens, bool)
+              and min_tokens >= 1))
+    if not ok:
+        raise ValueError("set_fp4_prefill: min_tokens must be None, "
+                         f"'measured' or an int >= 1, got {min_tokens!r}")
+    _FP4_PREFILL = min_tokens
+
+
+def _prefill_linear_fp4(x, w, b):
+    """The fp4 route of linear for a bf16 GPU x, or None where it does not
+    apply."""
+    o, i = w.shape
+    n = x.numel() // i
+    if i % 128 or o % 128:
+        return None
+    lo = (_FP4_PREFILL_ROUTES.get(_fp8_mfma_class(i, o))
+          if _FP4_PREFILL == "measured" else _FP4_PREFILL)
+    if lo is None or n < lo:
+        return None
+    ent = _FP4_WEIGHTS.get(w.data_ptr())
+    # data_ptr can be recycled after a free; require matching shape
+    if ent is None or tuple(ent[0].shape) != (o, i // 2):
+        return None
+    y = gemm_mxfp4_a8(x.reshape(n, i).contiguous(), ent[0], ent[1])
+    y = y.view(*x.shape[:-1], o)
+    return y if b is None else y + b
 
 
 def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
@@ -1287,4 +1413,6 @@ __all__ = [
     "skinny_gemm_fp8_mfma", "set_fp8_decode_max_batch",
     "quantize_mxfp4", "dequantize_mxfp4", "skinny_gemm_fp4_mfma",
     "register_fp4_weight", "clear_fp4_weights", "set_fp4_decode_max_batch",
+    "quantize_mxfp8", "dequantize_mxfp8", "quantize_mxfp8_rows",
+    "gemm_mxfp4_a8", "set_fp4_prefill",
 ]

@@ -52,6 +52,10 @@ void skinny_gemm_fp8_mfma_launch(const void*, const float*, const void*,
                                  void*, int, int, int, int, hipStream_t);
 void skinny_gemm_fp4_mfma_launch(const void*, const void*, const void*,
                                  void*, int, int, int, int, hipStream_t);
+void quantize_mxfp8_rows_launch(const void*, void*, void*, int, int, int,
+                                hipStream_t);
+void gemm_mxfp4_a8_launch(const void*, const void*, const void*, const void*,
+                          void*, int, int, int, int, hipStream_t);
 void gemm_nt_launch(const void*, const void*, void*, int, int, long long,
                     hipStream_t);
 void adamw_mt_launch(const void*, const void*, const void*, const void*,
@@ -1075,6 +1079,73 @@ torch::Tensor skinny_gemm_fp4_mfma(torch::Tensor X, torch::Tensor codes,
   return y;
 }
 
+// X [N, I] bf16 -> MXFP8 (gemm_mxfp4_a8.hip): codes uint8 [N_pad, I] e4m3fn,
+// exps uint8 [N_pad, I/32], N_pad = N rounded up to the GEMM's token tile of
+// 128; rows N..N_pad-1 are zero codes with exponent 127.
+static std::tuple<torch::Tensor, torch::Tensor> quantize_mxfp8_rows_checked(
+    const char* op, const torch::Tensor& X, int64_t k_multiple) {
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(N >= 1 && N <= std::numeric_limits<int>::max() - 128, op,
+              ": N must be at least 1, got ", N);
+  TORCH_CHECK(I >= k_multiple && I % k_multiple == 0 &&
+                  I <= std::numeric_limits<int>::max(),
+              op, ": I must be a positive multiple of ", k_multiple, ", got ",
+              I);
+  TORCH_CHECK(aligned16(X), op, ": X must start on a 16-byte boundary");
+  const int64_t Np = (N + 127) / 128 * 128;
+  auto q = torch::empty({Np, I}, X.options().dtype(at::kByte));
+  auto e = torch::empty({Np, I / 32}, X.options().dtype(at::kByte));
+  TORCH_CHECK(aligned16(q), op, ": the codes must start on a 16-byte boundary");
+  quantize_mxfp8_rows_launch(X.data_ptr(), q.data_ptr(), e.data_ptr(), (int)N,
+                             (int)Np, (int)I, cur_stream());
+  return {q, e};
+}
+
+std::tuple<torch::Tensor, torch::Tensor> quantize_mxfp8_rows(
+    torch::Tensor X) {
+  return quantize_mxfp8_rows_checked("quantize_mxfp8_rows", X, 32);
+}
+
+torch::Tensor gemm_mxfp4_a8(torch::Tensor X, torch::Tensor codes,
+                            torch::Tensor exps) {
+  // Y[N,O] = mxfp8(X)[N,I] @ W^T over MXFP4 weights (gemm_mxfp4_a8.hip):
+  // quantises X by blocks of 32 k, then runs the block-scaled MFMA GEMM.
+  // codes uint8 [O, I/2], exps uint8 [O, I/32] as skinny_gemm_fp4_mfma takes.
+  const char* op = "gemm_mxfp4_a8";
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(I >= 128 && I % 128 == 0, op,
+              ": I must be a positive multiple of 128, got ", I);
+  check_dense(op, "codes", codes, at::kByte, X);
+  TORCH_CHECK(codes.dim() == 2 && codes.size(1) == I / 2, op,
+              ": codes must be [O, I/2] with I/2 = ", I / 2, ", got ",
+              codes.sizes());
+  const int64_t O = codes.size(0);
+  TORCH_CHECK(O >= 128 && O % 128 == 0 &&
+                  O <= std::numeric_limits<int>::max(),
+              op, ": O must be a positive multiple of 128, got ", O);
+  check_dense(op, "exps", exps, at::kByte, X);
+  TORCH_CHECK(exps.dim() == 2 && exps.size(0) == O && exps.size(1) == I / 32,
+              op, ": exps must be [O, I/32] = [", O, ", ", I / 32, "], got ",
+              exps.sizes());
+  auto [xq, xe] = quantize_mxfp8_rows_checked(op, X, 128);
+  TORCH_CHECK(xq.size(0) / 128 <= 65535, op, ": N must be at most ",
+              65535 * 128, ", got ", N);
+  auto y = torch::empty({N, O}, X.options());
+  const torch::Tensor* ts[] = {&codes, &exps, &xe, &y};
+  const char* names[] = {"codes", "exps", "the scratch", "the output"};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(aligned16(*ts[i]), op, ": ", names[i],
+                " must start on a 16-byte boundary");
+  gemm_mxfp4_a8_launch(codes.data_ptr(), exps.data_ptr(), xq.data_ptr(),
+                       xe.data_ptr(), y.data_ptr(), (int)N, (int)xq.size(0),
+                       (int)I, (int)O, cur_stream());
+  return y;
+}
+
 torch::Tensor skinny_gemm(torch::Tensor X, torch::Tensor W) {
   // Y[N,O] = X[N,I] @ W[O,I]^T (decode GEMV; see skinny_gemm.hip)
   CHECK_GPU(X); CHECK_CONTIG(X); CHECK_BF16(X);
@@ -1417,6 +1488,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w8"), py::arg("scale"), py::arg("row_tiles") = 0);
   m.def("skinny_gemm_fp4_mfma", &skinny_gemm_fp4_mfma, py::arg("x"),
         py::arg("codes"), py::arg("exps"), py::arg("row_tiles") = 0);
+  m.def("quantize_mxfp8_rows", &quantize_mxfp8_rows, py::arg("x"));
+  m.def("gemm_mxfp4_a8", &gemm_mxfp4_a8, py::arg("x"), py::arg("codes"),
+        py::arg("exps"));
   m.def("transpose_bf16", &transpose_bf16);
   m.def("gemm_nt", &gemm_nt);
   m.def("wgrad_tn", &wgrad_tn);

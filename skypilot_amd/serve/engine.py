@@ -261,15 +261,36 @@ class Engine:
         """Quantize every large linear weight to MXFP4 (ops.quantize_mxfp4,
         4.25 bits per weight) and route decode batches of 1..max_batch
         tokens through the fp4 MFMA GEMM where its measured table has it
-        winning (ops.set_fp4_decode_max_batch); prefill stays bf16.  The
+        winning (ops.set_fp4_decode_max_batch); prefill stays bf16 unless
+        enable_fp4_prefill.  The
         weights are the ones enable_fp8_decode takes, with I % 128 == 0.
         One engine serves fp8 or fp4 decode weights, not both.  Returns the
         number of weights registered."""
         from skypilot_amd import ops as _ops
         self._claim_decode_weights("fp4")
         _ops.set_fp4_decode_max_batch(max_batch)
-        return self._register_decode_weights(_ops.register_fp4_weight,
-                                             min_bytes, 128)
+        self._fp4_registered = self._register_decode_weights(
+            _ops.register_fp4_weight, min_bytes, 128)
+        return self._fp4_registered
+
+    def enable_fp4_prefill(self, min_tokens="measured",
+                           min_bytes: int = 1 << 20) -> int:
+        """Serve prefill and prompt chunks of at least min_tokens tokens from
+        the MXFP4 weights too: ops.linear and ops.qkv_linear quantise their
+        input to MXFP8 and run the block-scaled MFMA GEMM
+        (ops.gemm_mxfp4_a8, ops.set_fp4_prefill).  "measured" takes the
+        per-shape thresholds of the benchmark, an int forces one.  Registers
+        the weights enable_fp4_decode would if they are not registered yet
+        (decode steps then read them as well); lm_head and the
+        tensor-parallel model keep bf16.  Returns the number of weights
+        registered."""
+        from skypilot_amd import ops as _ops
+        self._claim_decode_weights("fp4")
+        if getattr(self, "_fp4_registered", None) is None:
+            self._fp4_registered = self._register_decode_weights(
+                _ops.register_fp4_weight, min_bytes, 128)
+        _ops.set_fp4_prefill(min_tokens)
+        return self._fp4_registered
 
     def _claim_decode_weights(self, fmt: str) -> None:
         have = getattr(self, "_decode_weight_format", fmt)

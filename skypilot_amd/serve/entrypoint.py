@@ -294,6 +294,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--fp4-decode-max-batch", type=int, default=64,
                     help="with --fp4-decode: largest decode batch served "
                          "from the fp4 weights (1..64)")
+    ap.add_argument("--fp4-prefill", action="store_true",
+                    help="serve prefill and prompt chunks from the MXFP4 "
+                         "weights too (MXFP8 activations, block-scaled MFMA "
+                         "GEMM) where the measured table has it winning "
+                         "(docs/BENCHMARKS.md: nowhere yet); not with "
+                         "--fp8-decode or --tp")
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree; run under torchrun "
                          "with one rank per GPU (70B serving: --tp 8)")
@@ -368,6 +374,9 @@ def main():
     if args.fp4_decode:
         n4 = engine.enable_fp4_decode(max_batch=args.fp4_decode_max_batch)
         print(f"fp4 decode weights: {n4} tensors quantized", flush=True)
+    if args.fp4_prefill:
+        n4 = engine.enable_fp4_prefill()
+        print(f"fp4 prefill weights: {n4} tensors quantized", flush=True)
     engine.start()
     app = create_app(engine, args.model)
     print(f"serving {args.model} on {args.host}:{args.port} "
