@@ -1315,6 +1315,100 @@ def decode_logprobs(logits, stage, n_top, lp_ring, top_lp_ring, top_id_ring,
                       top_lp_ring, top_id_ring, ctr)
 
 
+# ---- decode penalties (docs/KERNELS.md "Decode penalties") -----------------
+PENALTY_MAX_SEQ = 65535   # generated and prompt counts share a 32-bit word
+
+
+def penalty_workspace(rows, vocab, device):
+    """The all-zero count workspace `cnt` uint32 [rows, vocab] of
+    penalize_logits.  Every call leaves it all zero again."""
+    return torch.zeros(rows, vocab, dtype=torch.int32,
+                       device=device).view(torch.uint32)
+
+
+def penalize_logits_reference(logits, hist, tok, pos, slot, prompt_len,
+                              presence, frequency, repetition):
+    """fp64 reference of the penalty definition, in plain torch.  logits
+    [n, V] (taken at their bf16 value), hist int32 [slots, S_max], four
+    index vectors and three fp32 parameter vectors of n entries.  Records
+    hist[slot, pos] = tok for the live rows, in place, and returns
+    (value fp64 [n, V], seen bool [n, V], count int64 [n, V]): the
+    unrounded penalised value where seen, the logit itself elsewhere, and
+    the generated count c_j.
+
+    Per live row (some parameter set, slot and pos inside hist): P is
+    clamped into [0, p + 1], c_j counts id j in hist[s, P..p], seen_j is
+    true for ids in hist[s, 0..p]; ids outside [0, V) are ignored.  For a
+    seen token x = l / rho if l > 0 else l * rho (when rho != 1), then
+    x - frequency * c - presence * [c > 0]."""
+    l2 = logits.detach().to("cpu").float().double()
+    l2 = l2.reshape(-1, l2.shape[-1])
+    n, V = l2.shape
+    slots, s_max = hist.shape
+
+    def ints(x):
+        return torch.as_tensor(x).detach().to("cpu").reshape(-1).tolist()
+
+    def f32s(x):
+        return torch.as_tensor(x).detach().to("cpu").to(
+            torch.float32).double().reshape(-1).tolist()
+
+    tok, pos, slot, prompt_len = (ints(x) for x in
+                                  (tok, pos, slot, prompt_len))
+    alpha, beta, rho = f32s(presence), f32s(frequency), f32s(repetition)
+    value = l2.clone()
+    seen = torch.zeros(n, V, dtype=torch.bool)
+    count = torch.zeros(n, V, dtype=torch.int64)
+    for i in range(n):
+        s, p = slot[i], pos[i]
+        if alpha[i] == 0 and beta[i] == 0 and rho[i] == 1:
+            continue
+        if not (0 <= s < slots and 0 <= p < s_max):
+            continue
+        hist[s, p] = tok[i]
+        P = min(max(prompt_len[i], 0), p + 1)
+        ids = hist[s, :p + 1].detach().to("cpu").long()
+        ok = (ids >= 0) & (ids < V)
+        seen[i, ids[ok]] = True
+        gen = ids[P:][ok[P:]]
+        count[i] = torch.bincount(gen, minlength=V)
+        l = l2[i]
+        x = l
+        if rho[i] != 1:
+            x = torch.where(l > 0, l / rho[i], l * rho[i])
+        c = count[i].double()
+        x = x - beta[i] * c - alpha[i] * (c > 0).double()
+        value[i] = torch.where(seen[i], x, l)
+    return value, seen, count
+
+
+def penalize_logits(logits, out, hist, cnt, tok, pos, slot, prompt_len,
+                    presence, frequency, repetition):
+    """out [n, V] = the bf16 logits [n, V] under each row's presence,
+    frequency and repetition penalty over the token history of its
+    sequence (decode_penalty.hip on GPU, the fp64 reference on CPU).
+    hist int32 [slots, S_max] holds token ids by position; the op first
+    records hist[slot, pos] = tok, then uses positions 0..pos, of which
+    the first prompt_len are the prompt (seen, but not counted).  tok,
+    pos, slot and prompt_len are int32 [n], the three parameters fp32
+    [n]; a row with presence == frequency == 0 and repetition == 1, or
+    with slot / pos outside hist, is copied bit for bit.  cnt is
+    penalty_workspace(>= n, V) (unused on CPU).  `out` must not alias
+    `logits`: the log-probability ops keep reading the raw row."""
+    if not logits.is_cuda:
+        value, seen, _ = penalize_logits_reference(
+            logits, hist, tok, pos, slot, prompt_len, presence, frequency,
+            repetition)
+        out.copy_(logits.reshape(out.shape))
+        out[seen.reshape(out.shape)] = value.float().to(
+            out.dtype).reshape(out.shape)[seen.reshape(out.shape)]
+        return out
+    C = _require_native("penalize_logits")
+    C.penalize_logits(logits, out, hist, cnt, tok, pos, slot, prompt_len,
+                      presence, frequency, repetition)
+    return out
+
+
 def decode_swiglu_down(gu, weight):
     """silu(gate)*up followed by the down projection.  MEASURED
     NEGATIVE as a fused GEMV (skinny_gemm_swiglu kept for reference):

@@ -40,6 +40,7 @@ HIP_SOURCES = [
     "wgrad_gemm.hip",
     "decode_fused.hip",
     "decode_sample.hip",
+    "decode_penalty.hip",
     "mfma_probe.hip",
 ]
 CPP_SOURCES = ["bindings.cpp"]

@@ -73,6 +73,10 @@ void decode_logprobs_launch(const void*, int, const void*, long long,
 void decode_sample_advance_launch(const void*, int, void*, long long, void*,
                                   const void*, int, const void*,
                                   hipStream_t);
+void penalize_logits_launch(const void*, void*, int, long long, void*, int,
+                            int, void*, const void*, const void*, const void*,
+                            const void*, const void*, const void*,
+                            const void*, hipStream_t);
 void rmsnorm_res_launch(const void*, const void*, const void*, void*, void*,
                         int, int, float, hipStream_t);
 void rope_kvwrite_launch(const void*, void*, void*, void*, const void*,
@@ -1377,6 +1381,87 @@ void decode_logprobs(torch::Tensor logits, torch::Tensor stage,
                            ctr.data_ptr(), (int)chunk, cur_stream());
 }
 
+// ---- decode penalties (decode_penalty.hip) --------------------------------
+// The byte ranges of two dense tensors overlap.
+static bool overlaps(const torch::Tensor& a, const torch::Tensor& b) {
+  const char* a0 = (const char*)a.data_ptr();
+  const char* b0 = (const char*)b.data_ptr();
+  return a.nbytes() > 0 && b.nbytes() > 0 && a0 < b0 + b.nbytes() &&
+         b0 < a0 + a.nbytes();
+}
+
+// out [n, V] = logits [n, V] under the presence / frequency / repetition
+// penalties of each row's token history; records hist[slot, pos] = tok for
+// the live rows.  cnt is the all-zero count workspace and is all zero
+// again afterwards.  The values of tok / pos / slot / prompt_len are not
+// read on the host: the kernel treats a slot or position outside hist as
+// an off row.
+void penalize_logits(torch::Tensor logits, torch::Tensor out,
+                     torch::Tensor hist, torch::Tensor cnt, torch::Tensor tok,
+                     torch::Tensor pos, torch::Tensor slot,
+                     torch::Tensor prompt_len, torch::Tensor presence,
+                     torch::Tensor frequency, torch::Tensor repetition) {
+  const char* op = "penalize_logits";
+  check_dense(op, "logits", logits, at::kBFloat16, logits);
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be [n, V], got ",
+              logits.sizes());
+  const int64_t n = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V <= kSampleMaxV, op,
+              ": V must be in [1, 2^23], got ", V);
+  TORCH_CHECK(n <= std::numeric_limits<int>::max(), op, ": ", n,
+              " rows exceed the grid limit 2^31 - 1");
+  check_dense(op, "out", out, at::kBFloat16, logits);
+  TORCH_CHECK(out.sizes() == logits.sizes(), op,
+              ": out must have logits' shape ", logits.sizes(), ", got ",
+              out.sizes());
+  check_dense(op, "hist", hist, at::kInt, logits);
+  TORCH_CHECK(hist.dim() == 2 && hist.size(0) >= 1 && hist.size(1) >= 1 &&
+                  hist.size(0) <= std::numeric_limits<int>::max(),
+              op, ": hist must be [slots >= 1, S_max >= 1], got ",
+              hist.sizes());
+  // generated and prompt counts share a 32-bit word, 16 bits each
+  TORCH_CHECK(hist.size(1) <= 65535, op,
+              ": S_max = hist.size(1) must be at most 65535, got ",
+              hist.size(1));
+  check_dense(op, "cnt", cnt, at::kUInt32, logits);
+  TORCH_CHECK(cnt.dim() == 2 && cnt.size(0) >= n && cnt.size(1) == V, op,
+              ": cnt must be [b_max >= n, V] = [>= ", n, ", ", V, "], got ",
+              cnt.sizes());
+  check_index(op, "tok", tok, n, logits);
+  check_index(op, "pos", pos, n, logits);
+  check_index(op, "slot", slot, n, logits);
+  check_index(op, "prompt_len", prompt_len, n, logits);
+  const torch::Tensor* ps[] = {&presence, &frequency, &repetition};
+  const char* pnames[] = {"presence", "frequency", "repetition"};
+  for (int i = 0; i < 3; ++i) {
+    check_dense(op, pnames[i], *ps[i], at::kFloat, logits);
+    TORCH_CHECK(ps[i]->dim() == 1 && ps[i]->size(0) == n, op, ": ",
+                pnames[i], " must be a [n] = [", n, "] tensor, got ",
+                ps[i]->sizes());
+  }
+  // what the kernel writes must not overlap anything else it touches
+  const torch::Tensor* ws[] = {&out, &hist, &cnt};
+  const char* wnames[] = {"out", "hist", "cnt"};
+  const torch::Tensor* as[] = {&logits,   &out,       &hist,      &cnt,
+                               &tok,      &pos,       &slot,      &prompt_len,
+                               &presence, &frequency, &repetition};
+  const char* anames[] = {"logits",   "out",       "hist",      "cnt",
+                          "tok",      "pos",       "slot",      "prompt_len",
+                          "presence", "frequency", "repetition"};
+  for (int w = 0; w < 3; ++w)
+    for (int a = 0; a < 11; ++a)
+      TORCH_CHECK(ws[w] == as[a] || !overlaps(*ws[w], *as[a]), op, ": ",
+                  wnames[w], " must not alias ", anames[a]);
+  if (n > 0)
+    penalize_logits_launch(logits.data_ptr(), out.data_ptr(), (int)V, n,
+                           hist.data_ptr(), (int)hist.size(0),
+                           (int)hist.size(1), cnt.data_ptr(), tok.data_ptr(),
+                           pos.data_ptr(), slot.data_ptr(),
+                           prompt_len.data_ptr(), presence.data_ptr(),
+                           frequency.data_ptr(), repetition.data_ptr(),
+                           cur_stream());
+}
+
 torch::Tensor rope_kvwrite(torch::Tensor qkv, torch::Tensor kc,
                            torch::Tensor vc, torch::Tensor cos_tab,
                            torch::Tensor sin_tab, torch::Tensor positions,
@@ -1508,6 +1593,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("decode_sample_advance", &decode_sample_advance);
   m.def("token_logprobs", &token_logprobs);
   m.def("decode_logprobs", &decode_logprobs);
+  m.def("penalize_logits", &penalize_logits);
   m.def("attn_decode_qkv", &attn_decode_qkv);
   m.def("kv_write_fp8", &kv_write_fp8);
   m.def("attn_decode_qkv_fp8", &attn_decode_qkv_fp8);

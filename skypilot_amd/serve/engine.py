@@ -25,6 +25,14 @@ distribution, temperature 1 and no filter, whatever the request samples
 with (ops.token_logprobs; docs/KERNELS.md "Token log-probabilities").
 In the graph path ops.decode_logprobs is captured behind the advance
 kernel and its rings are read in the chunk's one sync.
+
+With ``penalties`` set, requests may carry ``presence_penalty``,
+``frequency_penalty`` and ``repetition_penalty``: the engine keeps every
+sequence's token ids by position in ``hist`` and ops.penalize_logits
+(docs/KERNELS.md "Decode penalties") writes a penalised copy of the
+logits that the sampler or the argmax reads, inside the decode graph and
+in the eager steps alike.  Log-probabilities keep describing the raw
+logits.
 """
 from __future__ import annotations
 
@@ -102,6 +110,13 @@ class Request:
     # N); prompt_logprobs: also score the prompt's own tokens.
     logprobs: Optional[int] = None
     prompt_logprobs: bool = False
+    # Penalties need Engine(penalties=True).  presence and frequency act
+    # on the tokens generated so far, repetition (> 0, 1 is off) on every
+    # token of the prompt and the output (docs/KERNELS.md "Decode
+    # penalties").
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
     stream_queue: Optional["queue.Queue"] = None  # per-token streaming
     id: str = field(default_factory=lambda: uuid.uuid4().hex[:12])
     out_ids: List[int] = field(default_factory=list)
@@ -135,7 +150,11 @@ class Engine:
                  prefill_chunk: Optional[int] = None,
                  device_sampling: bool = False,
                  kv_dtype: str = "bf16", max_logprobs: int = 0,
-                 decode_attn: str = "per_head"):
+                 decode_attn: str = "per_head", penalties: bool = False):
+        # False keeps the decode graph, the staged block and every code
+        # path as they are without the feature, and submit() rejects a
+        # request that sets a penalty.
+        self.penalties = bool(penalties)
         # "grouped" runs decode attention through the grouped split-KV
         # kernel (docs/KERNELS.md "Grouped split-KV decode"); the default
         # keeps the per-head kernels and the decode graph as they are.
@@ -240,6 +259,23 @@ class Engine:
         if self.use_graphs:
             self._scratch_slot = self.free_slots.pop()
             self.max_batch -= 1
+        # Penalties: token ids by position for every cache slot, and on
+        # the GPU the kernel's all-zero count workspace, sized for the
+        # largest graph bucket and shared by all buckets and by the eager
+        # steps (one step runs at a time, and each leaves it all zero).
+        self.hist: Optional[torch.Tensor] = None
+        self._pen_cnt: Optional[torch.Tensor] = None
+        if self.penalties:
+            if self.max_seq > ops.PENALTY_MAX_SEQ:
+                raise ValueError(
+                    f"penalties need max_seq <= {ops.PENALTY_MAX_SEQ}, got "
+                    f"{self.max_seq}")
+            self.hist = torch.zeros(self.cache.max_batch, self.max_seq,
+                                    dtype=torch.int32, device=self.device)
+            if self.device.type == "cuda":
+                self._pen_cnt = ops.penalty_workspace(
+                    self._bucket(max(self.max_batch, 1)),
+                    self.cfg.vocab_size, self.device)
 
     def enable_fp8_decode(self, min_bytes: int = 1 << 20,
                           max_batch: int = 2) -> int:
@@ -331,6 +367,7 @@ class Engine:
     def submit(self, req: Request) -> Request:
         self._check_sampling(req)
         self._check_logprobs(req)
+        self._check_penalties(req)
         if len(req.prompt_ids) >= self.max_seq:
             req.prompt_ids = req.prompt_ids[-(self.max_seq - 1 -
                                               req.max_tokens):]
@@ -397,6 +434,65 @@ class Engine:
             raise ValueError(
                 f"logprobs = {n} exceeds this engine's max_logprobs = "
                 f"{self.max_logprobs}")
+
+    def _check_penalties(self, req: Request) -> None:
+        """Validate and normalise a request's penalties to plain finite
+        floats, as _check_sampling does.  Raises ValueError."""
+        for name in ("presence_penalty", "frequency_penalty",
+                     "repetition_penalty"):
+            v = getattr(req, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise ValueError(f"{name} must be a number, got {v!r}")
+            try:
+                v = float(v)
+            except OverflowError:
+                v = math.inf
+            if not math.isfinite(v):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+            setattr(req, name, v)
+        if req.repetition_penalty <= 0:
+            raise ValueError("repetition_penalty must be > 0, got "
+                             f"{req.repetition_penalty!r}")
+        if not self.penalties and self._pen_row(req)[:3] != (0.0, 0.0, 1.0):
+            # refuse rather than drop them
+            raise ValueError(
+                "presence_penalty, frequency_penalty and repetition_penalty "
+                "need an engine with penalties on (Engine(penalties=True) / "
+                "--penalties)")
+
+    @staticmethod
+    def _pen_row(req: Request) -> tuple:
+        """(presence, frequency, repetition, prompt length): one row of
+        the penalty parameters, what the TP decode plan carries."""
+        return (req.presence_penalty, req.frequency_penalty,
+                req.repetition_penalty, len(req.prompt_ids))
+
+    def _pen_rows(self, reqs: List[Request]):
+        return [self._pen_row(r) for r in reqs] if self.penalties else None
+
+    def _hist_put(self, slot: int, start: int, ids: List[int]) -> None:
+        """Admission: prompt ids into hist[slot, start:start + len(ids)]."""
+        if self.penalties and ids:
+            self.hist[slot, start:start + len(ids)] = torch.tensor(
+                ids, dtype=torch.int32, device=self.device)
+
+    def _penalize(self, logits: torch.Tensor, pen, slots: List[int],
+                  positions: List[int], toks: List[int]) -> torch.Tensor:
+        """The eager steps' ops.penalize_logits: `logits` [n, V] of the
+        tokens `toks` at `positions` of cache slots `slots`, `pen` the
+        rows of _pen_rows.  Returns the penalised copy, or `logits`
+        itself when no row sets a penalty (hist is then left alone, as
+        the op leaves it for an off row)."""
+        if pen is None or all(r[:3] == (0.0, 0.0, 1.0) for r in pen):
+            return logits
+        idx = torch.tensor([toks, positions, slots, [r[3] for r in pen]],
+                           dtype=torch.int32, device=self.device)
+        par = torch.tensor([[r[k] for r in pen] for k in range(3)],
+                           dtype=torch.float32, device=self.device)
+        logits = logits.contiguous()
+        return ops.penalize_logits(
+            logits, torch.empty_like(logits), self.hist, self._pen_cnt,
+            idx[0], idx[1], idx[2], idx[3], par[0], par[1], par[2])
 
     def _record_logprobs(self, logits: torch.Tensor, reqs: List[Request],
                          ids: List[int]) -> None:
@@ -478,7 +574,14 @@ class Engine:
                                prefill_slots=slots, prefill_lens=lens)
         logits = self.model(toks, positions, ctx)
         last = logits[torch.arange(n), torch.tensor(lens) - 1]  # [n, V]
-        first = self._sample_batch(last, reqs, [l - 1 for l in lens])
+        for slot, r in zip(slots, reqs):
+            self._hist_put(slot, 0, r.prompt_ids)
+        # the first token is drawn under the prompt's penalties: the input
+        # token is the prompt's last, nothing is generated yet
+        pen = self._penalize(last, self._pen_rows(reqs), slots,
+                             [l - 1 for l in lens],
+                             [r.prompt_ids[-1] for r in reqs])
+        first = self._sample_batch(pen, reqs, [l - 1 for l in lens])
         self._record_logprobs(last, reqs, first)
         for i, req in enumerate(reqs):
             if req.prompt_logprobs:
@@ -512,6 +615,7 @@ class Engine:
         for i, ids in enumerate(chunks):
             toks[i, :lens[i]] = torch.tensor(ids, dtype=torch.long,
                                              device=self.device)
+            self._hist_put(slots[i], starts[i], ids)
 
         def i32(vals):
             return torch.tensor(vals, dtype=torch.int32, device=self.device)
@@ -561,8 +665,12 @@ class Engine:
         first = {}
         if fin:
             fin_reqs = [batch[i].req for i in fin]
-            fin_ids = self._sample_batch(logits[fin, 0], fin_reqs,
-                                         [ends[i] - 1 for i in fin])
+            fin_pos = [ends[i] - 1 for i in fin]
+            pen = self._penalize(
+                logits[fin, 0], self._pen_rows(fin_reqs),
+                [slots[i] for i in fin], fin_pos,
+                [r.prompt_ids[-1] for r in fin_reqs])
+            fin_ids = self._sample_batch(pen, fin_reqs, fin_pos)
             self._record_logprobs(logits[fin, 0], fin_reqs, fin_ids)
             first = dict(zip(fin, fin_ids))
         for i, e in enumerate(batch):
@@ -609,7 +717,11 @@ class Engine:
         # the same copy.
         # With max_logprobs > 0 one more row at the end holds each
         # sequence's n_top (-1: did not ask, and padding).
-        rows = (11 if self.device_sampling else 6) + (
+        # With penalties four rows follow the sampling parameters:
+        # presence bits, frequency bits, repetition bits, prompt length
+        # (padding rows: 0, 0, 1.0, 0 — off).
+        nsamp = 11 if self.device_sampling else 6
+        rows = nsamp + (4 if self.penalties else 0) + (
             1 if self.max_logprobs else 0)
         st = {
             "host": torch.zeros(rows, b, dtype=torch.int32,
@@ -617,7 +729,13 @@ class Engine:
             "block": torch.zeros(rows, b, dtype=torch.int32, device=dev),
         }
         st["stage"] = st["block"][:6]
-        st["samp"] = st["block"][6:11 if self.device_sampling else 6]
+        st["samp"] = st["block"][6:nsamp]
+        if self.penalties:
+            st["pen"] = st["block"][nsamp:nsamp + 4]
+            st["pen"][2] = torch.ones(
+                b, device=dev).view(torch.int32)  # repetition 1.0
+            st["pen_out"] = torch.empty(b, self.cfg.vocab_size,
+                                        dtype=torch.bfloat16, device=dev)
         if self.max_logprobs:
             st["ntop"] = st["block"][rows - 1]
             st["ntop"].fill_(-1)
@@ -664,13 +782,21 @@ class Engine:
             # profiles/r02_fp8_decode_kernel_stats.txt).  The ctr
             # increment stays a separate captured op so the kernel's
             # ring-row read is ordered before it.
+            # With penalties the advance kernel reads the penalised copy
+            # of the logits: the input token stage[0] at position stage[1]
+            # goes into hist, and the row's history decides the values.
+            src = st["out"][:, 0]
+            if self.penalties:
+                stg, pen = st["stage"], st["pen"]
+                src = ops.penalize_logits(
+                    src, st["pen_out"], self.hist, self._pen_cnt, stg[0],
+                    stg[1], stg[5], pen[3], pen[0].view(torch.float32),
+                    pen[1].view(torch.float32), pen[2].view(torch.float32))
             if self.device_sampling:
-                ops.decode_sample_advance(st["out"][:, 0], st["stage"],
-                                          st["ring"], st["ctr"],
-                                          st["samp"])
+                ops.decode_sample_advance(src, st["stage"], st["ring"],
+                                          st["ctr"], st["samp"])
             else:
-                ops.decode_advance(st["out"][:, 0], st["stage"],
-                                   st["ring"], st["ctr"])
+                ops.decode_advance(src, st["stage"], st["ring"], st["ctr"])
             # Log-probabilities of the token just chosen (stage[0]), from
             # the same logits, into ring row ctr % CHUNK: after the
             # advance kernel and before the ctr increment.
@@ -693,6 +819,8 @@ class Engine:
         n = len(slots)
         lens = [self.cache.lens[s] for s in slots]
         tok_l = [r.out_ids[-1] for r in reqs]
+        pen = self._pen_rows(reqs)
+        penalised = None  # [n, V] when the graph has made it already
         if self.use_graphs:
             b = self._bucket(n)
             all_greedy = all(r.temperature == 0 for r in reqs)
@@ -717,7 +845,8 @@ class Engine:
             want_lp = ntop is not None and any(v >= 0 for v in ntop)
             self._tp_bcast({"op": "decode", "graph": True, "bucket": b,
                             "slots": slots, "lens": lens, "toks": tok_l,
-                            "chunk": chunk, "samp": samp, "ntop": ntop})
+                            "chunk": chunk, "samp": samp, "ntop": ntop,
+                            "pen": pen})
             try:
                 g, st = self._get_graph(b)
             except Exception as e:  # capture unsupported -> eager forever
@@ -728,7 +857,7 @@ class Engine:
                       f"to eager decode: {e!r}", file=sys.stderr)
                 self.use_graphs = False
                 return self._decode_step()
-            self._stage_inputs(st, slots, lens, tok_l, samp, ntop)
+            self._stage_inputs(st, slots, lens, tok_l, samp, ntop, pen)
             for _ in range(chunk):
                 g.replay()
             if chain:
@@ -754,10 +883,13 @@ class Engine:
                         self._maybe_finish(slot, req, next_id)
                 return
             logits = st["out"]  # [b, 1, V]
+            if self.penalties:
+                penalised = st["pen_out"][:n]
         else:
             self._tp_bcast({"op": "decode", "graph": False,
                             "slots": slots, "lens": lens, "toks": tok_l,
-                            "chunk": 1, "samp": self._samp_rows(reqs)})
+                            "chunk": 1, "samp": self._samp_rows(reqs),
+                            "pen": pen})
             toks = torch.tensor([[t] for t in tok_l], dtype=torch.long,
                                 device=self.device)
             slots_t = torch.tensor(slots, dtype=torch.long,
@@ -777,14 +909,19 @@ class Engine:
         # the host path greedy rows batch into one argmax + one sync and
         # sampled rows (temperature > 0) go through _sample individually.
         # (The chained graph path already returned above.)
+        # Tokens come from the penalised logits (the input token of each
+        # row sits at position lens[i]); log-probabilities from the raw.
+        if penalised is None:
+            penalised = self._penalize(logits[:n, 0], pen, slots, lens,
+                                       tok_l)
         batch_ids = None
         if self.device_sampling:
             # counter = position of each row's input token
-            batch_ids = self._sample_batch(logits[:n, 0], reqs, lens)
+            batch_ids = self._sample_batch(penalised, reqs, lens)
         elif all(r.temperature == 0 for r in reqs):
-            batch_ids = logits[:n, 0].argmax(-1).tolist()
+            batch_ids = penalised.argmax(-1).tolist()
         if batch_ids is None:
-            batch_ids = [self._sample(logits[i, 0], r.temperature, r.top_p)
+            batch_ids = [self._sample(penalised[i], r.temperature, r.top_p)
                          for i, r in enumerate(reqs)]
         self._record_logprobs(logits[:n, 0], reqs, batch_ids)
         for i, slot in enumerate(slots):
@@ -805,7 +942,7 @@ class Engine:
         return [(r.temperature, r.top_p, r.top_k, r.seed) for r in reqs]
 
     def _stage_inputs(self, st, slots, lens, tok_l, samp,
-                      ntop=None) -> None:
+                      ntop=None, pen=None) -> None:
         """Fill the pinned host block for one graph step and start its
         copy to the device (the leader and the TP followers share this).
         Padding rows point at the scratch slot and are greedy."""
@@ -830,6 +967,15 @@ class Engine:
             hu[9, :n] = [r[3] & 0xFFFFFFFF for r in samp]
             hu[10, :n] = [r[3] >> 32 for r in samp]
             h[6:, n:] = 0  # temperature 0: padding rows take the argmax
+        if self.penalties:
+            k = 11 if self.device_sampling else 6
+            hf = h.view("float32")
+            for j in range(3):
+                hf[k + j, :n] = [r[j] for r in pen]
+            h[k + 3, :n] = [r[3] for r in pen]
+            hf[k:k + 2, n:] = 0.0  # padding rows are off
+            hf[k + 2, n:] = 1.0
+            h[k + 3, n:] = 0
         if self.max_logprobs:
             h[-1, :n] = ntop if ntop is not None else -1
             h[-1, n:] = -1
@@ -909,6 +1055,7 @@ class Engine:
         toks = torch.zeros(n, pad, dtype=torch.long, device=self.device)
         for i, ids in enumerate(msg["prompts"]):
             toks[i, :lens[i]] = torch.tensor(ids, device=self.device)
+            self._hist_put(slots[i], 0, ids)
         positions = torch.arange(pad, dtype=torch.int32,
                                  device=self.device).repeat(n)
         ctx = InferenceContext(cache=self.cache, mode="prefill",
@@ -926,7 +1073,7 @@ class Engine:
         if msg["graph"]:
             g, st = self._get_graph(msg["bucket"])
             self._stage_inputs(st, slots, lens, tok_l, msg.get("samp"),
-                               msg.get("ntop"))
+                               msg.get("ntop"), msg.get("pen"))
             for _ in range(msg["chunk"]):
                 g.replay()
             torch.cuda.synchronize()
@@ -943,7 +1090,9 @@ class Engine:
                                slots=slots_t, pos=pos_t, kv_lens=kv_lens,
                                slot_ids_i32=slots_t.int(),
                                decode_attn=self.decode_attn)
-        self.model(toks, positions, ctx)
+        logits = self.model(toks, positions, ctx)
+        # keeps this rank's hist equal to the leader's
+        self._penalize(logits[:, 0], msg.get("pen"), slots, lens, tok_l)
 
     def _loop(self):
         try:

@@ -21,7 +21,7 @@ from typing import List, Optional
 
 import uvicorn
 from fastapi import FastAPI, HTTPException
-from pydantic import BaseModel
+from pydantic import BaseModel, Field
 
 from skypilot_amd.serve.engine import Engine, Request
 
@@ -65,6 +65,11 @@ class CompletionRequest(BaseModel):
     top_p: float = 1.0
     top_k: int = 0
     seed: Optional[int] = None
+    # penalties need a server started with --penalties (docs/KERNELS.md
+    # "Decode penalties"); presence and frequency take the OpenAI range
+    presence_penalty: float = Field(0.0, ge=-2.0, le=2.0)
+    frequency_penalty: float = Field(0.0, ge=-2.0, le=2.0)
+    repetition_penalty: float = Field(1.0, gt=0.0)
     stop: Optional[List[str]] = None
     stream: bool = False
     # number of alternatives per token (0: the chosen token only); needs
@@ -87,6 +92,11 @@ class ChatRequest(BaseModel):
     top_p: float = 1.0
     top_k: int = 0
     seed: Optional[int] = None
+    # penalties need a server started with --penalties (docs/KERNELS.md
+    # "Decode penalties"); presence and frequency take the OpenAI range
+    presence_penalty: float = Field(0.0, ge=-2.0, le=2.0)
+    frequency_penalty: float = Field(0.0, ge=-2.0, le=2.0)
+    repetition_penalty: float = Field(1.0, gt=0.0)
     logprobs: bool = False
     top_logprobs: Optional[int] = None
 
@@ -116,7 +126,10 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
         r = Request(prompt_ids=ids, max_tokens=req.max_tokens,
                     temperature=req.temperature, top_p=req.top_p,
                     top_k=req.top_k, seed=req.seed, logprobs=logprobs,
-                    prompt_logprobs=prompt_logprobs)
+                    prompt_logprobs=prompt_logprobs,
+                    presence_penalty=req.presence_penalty,
+                    frequency_penalty=req.frequency_penalty,
+                    repetition_penalty=req.repetition_penalty)
         try:
             engine.submit(r)
         except ValueError as e:
@@ -161,7 +174,10 @@ def create_app(engine: Engine, model_name: str) -> FastAPI:
                      max_tokens=req.max_tokens,
                      temperature=req.temperature, top_p=req.top_p,
                      top_k=req.top_k, seed=req.seed, stream_queue=q,
-                     logprobs=req.logprobs)
+                     logprobs=req.logprobs,
+                     presence_penalty=req.presence_penalty,
+                     frequency_penalty=req.frequency_penalty,
+                     repetition_penalty=req.repetition_penalty)
             try:
                 engine.submit(r)
             except ValueError as e:
@@ -279,6 +295,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="let requests ask for token log-probabilities "
                          "with up to this many alternatives per token "
                          "(at most 20); 0, the default, leaves them off")
+    ap.add_argument("--penalties", action="store_true",
+                    help="let requests set presence_penalty, "
+                         "frequency_penalty and repetition_penalty: the "
+                         "penalty kernel runs inside the decode graph "
+                         "(costs one copy of the logits per step, and "
+                         "4 bytes per slot and position of history)")
     ap.add_argument("--device", default=None)
     ap.add_argument("--fp8-decode", action="store_true",
                     help="quantize weights to rowwise e4m3fn for the "
@@ -345,7 +367,8 @@ def main():
                         device_sampling=args.device_sampling,
                         kv_dtype=args.kv_dtype,
                         decode_attn=args.decode_attn,
-                        max_logprobs=args.max_logprobs)
+                        max_logprobs=args.max_logprobs,
+                        penalties=args.penalties)
         if args.fp8_decode:
             engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         if args.fp4_decode:
@@ -367,7 +390,8 @@ def main():
                     device_sampling=args.device_sampling,
                     kv_dtype=args.kv_dtype,
                     decode_attn=args.decode_attn,
-                        max_logprobs=args.max_logprobs)
+                    max_logprobs=args.max_logprobs,
+                    penalties=args.penalties)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
