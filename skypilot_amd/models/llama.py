@@ -171,6 +171,26 @@ class Attention(nn.Module):
         else:
             B, S, _ = x.shape
         decode = infer_ctx is not None and infer_ctx.mode == "decode"
+        if infer_ctx is not None and infer_ctx.mode == "verify":
+            # Speculative decoding: B = n * T rows, row b * T + t the token
+            # at position verify_start[b] + t of sequence b.  Packed qkv as
+            # in decode, then rope + scatter of all rows' K/V
+            # (decode_fused.hip) and attention of each sequence's T tokens
+            # over the cache it now holds (attention_verify.hip).
+            cache, li, T = infer_ctx.cache, self.layer_idx, infer_ctx.verify_t
+            if qkv is None:
+                qkv = ops.decode_linear(x.reshape(B, -1), self.packed_qkv())
+            qkv = qkv.reshape(B, -1)
+            if self._bqkv is not None:
+                qkv = qkv + self._bqkv
+            q = ops.rope_kvwrite(qkv, cache.k[li], cache.v[li], cos, sin,
+                                 positions, infer_ctx.verify_row_slots,
+                                 self.n_q, self.n_kv)
+            o = ops.attn_verify(q.view(B // T, T, self.n_q, d), cache.k[li],
+                                cache.v[li], infer_ctx.slot_ids_i32,
+                                infer_ctx.verify_start, self.scale)
+            return ops.decode_linear(o.reshape(B, self.n_q * d),
+                                     self.wo.weight).view(B, S, -1)
         if decode:
             # One packed qkv GEMV, then one fused rope+cache-write
             # kernel (decode_fused.hip) — replaces 3 GEMVs + rope x2 +
@@ -296,8 +316,13 @@ class Llama(nn.Module):
             positions = torch.arange(S, dtype=torch.int32,
                                      device=tokens.device)
             positions = positions.unsqueeze(0).expand(B, S).reshape(-1)
+        verify = infer_ctx is not None and infer_ctx.mode == "verify"
+        if verify:
+            # tokens [n, T] ride the decode loop as n * T one-token rows;
+            # the logits go back as [n, T, V]
+            tokens = tokens.reshape(-1, 1)
         x = self.embed(tokens)
-        if infer_ctx is not None and infer_ctx.mode == "decode":
+        if verify or (infer_ctx is not None and infer_ctx.mode == "decode"):
             # Fused-residual decode loop: every residual add rides in
             # the next rmsnorm_res kernel (one launch instead of two),
             # including the final-norm + lm-head hand-off.
@@ -329,7 +354,7 @@ class Llama(nn.Module):
             _, logits = ops.decode_norm_linear(
                 x, res, self.final_norm, self.cfg.norm_eps,
                 self.lm_head.weight)
-            return logits
+            return logits.view(B, S, -1) if verify else logits
         for blk in self.blocks:
             x = blk(x, cos, sin, positions, infer_ctx)
         if (infer_ctx is not None and infer_ctx.mode == "append"

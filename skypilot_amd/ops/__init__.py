@@ -1473,6 +1473,28 @@ def attn_decode_qkv_gqa_fp8(qkv, kc, vc, ke, ve, cos, sin, positions,
                                kv_lens, slot_ids, Hq, Hkv, scale)
 
 
+VERIFY_MAX_COLS = 32  # T * (Hq / Hkv) the verify kernel takes (two MFMA tiles)
+
+
+def attn_verify(q, kc, vc, slot_ids, q_start, scale, split_rows=-1):
+    """Attention of T = q.shape[1] >= 2 new tokens per sequence over the
+    bf16 slot KV cache (speculative decoding's verify step,
+    attention_verify.hip; no autograd): attn_append_ref with q_lens = T.
+    q [n, T, Hq, 128] is roped, the T new K/V rows are already in the cache
+    at [slot, q_start : q_start + T), and token t attends rows
+    kv <= q_start + t.  slot_ids / q_start are int32 [n] tensors on q's
+    device, never read on the host: the caller guarantees 0 <= slot < slots
+    and q_start + T <= S_max.  T * (Hq / Hkv) <= VERIFY_MAX_COLS;
+    split_rows as in attn_decode_qkv_gqa."""
+    if q.is_cuda:
+        C = _require_native("attn_verify")
+        return C.attn_verify(q.contiguous(), kc, vc, slot_ids, q_start,
+                             scale, split_rows)
+    n, T = q.shape[:2]
+    return attn_append_ref(q, kc, vc, slot_ids, q_start,
+                           torch.full((n,), T, dtype=torch.int32), scale)
+
+
 def rope_kvwrite(qkv, kc, vc, cos, sin, positions, slot_ids, Hq, Hkv):
     """Packed-qkv rope + KV-cache scatter (decode_fused.hip): applies
     rope to the q and k segments of qkv [n, (Hq+2*Hkv)*D], writes the
@@ -1504,6 +1526,7 @@ __all__ = [
     "kv_quantize", "kv_dequantize", "kv_write_fp8", "attn_decode_qkv_fp8",
     "attn_append_fp8", "attn_decode_fp8",
     "attn_decode_qkv_gqa", "attn_decode_qkv_gqa_fp8",
+    "attn_verify", "VERIFY_MAX_COLS",
     "skinny_gemm_fp8_mfma", "set_fp8_decode_max_batch",
     "quantize_mxfp4", "dequantize_mxfp4", "skinny_gemm_fp4_mfma",
     "register_fp4_weight", "clear_fp4_weights", "set_fp4_decode_max_batch",

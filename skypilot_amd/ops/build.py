@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "attention_decode.hip",
     "attention_decode_fp8.hip",
     "attention_decode_gqa.hip",
+    "attention_verify.hip",
     "attention_append.hip",
     "kv_write_fp8.hip",
     "swiglu.hip",
@@ -44,13 +45,14 @@ HIP_SOURCES = [
     "mfma_probe.hip",
 ]
 CPP_SOURCES = ["bindings.cpp"]
-# Extra flags per device TU.  The grouped decode kernel, the fp8 and fp4
+# Extra flags per device TU.  The grouped decode and verify kernels, the fp8 and fp4
 # MFMA decode GEMMs and the MXFP4 x MXFP8 prefill GEMM are built without packed-fp32 instructions (v_pk_mul_f32 and
 # kin): their fp32 vector math is then plain scalar-lane VALU code whatever
 # the optimiser would pick.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "attention_decode_gqa.hip": _NO_PK_F32,
+    "attention_verify.hip": _NO_PK_F32,
     "skinny_gemm_fp8_mfma.hip": _NO_PK_F32,
     "skinny_gemm_fp4_mfma.hip": _NO_PK_F32,
     "gemm_mxfp4_a8.hip": _NO_PK_F32,

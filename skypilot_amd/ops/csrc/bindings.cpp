@@ -13,6 +13,7 @@
 
 #include "attn_append.h"
 #include "attn_decode_gqa.h"
+#include "attn_verify.h"
 #include "attn_launch.h"
 #include "kv_fp8_launch.h"
 
@@ -735,6 +736,49 @@ torch::Tensor attn_decode_qkv_gqa_fp8(torch::Tensor qkv, torch::Tensor Kc,
       sin_tab.data_ptr(), positions.data_ptr<int>(), kv_lens.data_ptr<int>(),
       slot_ids.data_ptr<int>(), (int)B, S_max, (int)Hq, (int)Hkv, R,
       (int)splits, (float)scale, cur_stream());
+  return O;
+}
+
+// ---- multi-token verify attention (attention_verify.hip) -------------------
+// Q [n, T, Hq, 128] roped bf16 over the bf16 slot cache; the T new K/V rows
+// are already in the cache.  slot_ids / q_start stay on the device.
+torch::Tensor attn_verify(torch::Tensor Q, torch::Tensor Kc, torch::Tensor Vc,
+                          torch::Tensor slot_ids, torch::Tensor q_start,
+                          double scale, int64_t split_rows) {
+  const char* op = "attn_verify";
+  check_dense(op, "Q", Q, at::kBFloat16, Q);
+  TORCH_CHECK(Q.dim() == 4 && Q.size(3) == ATT_D, op,
+              ": Q must be [n, T, Hq, 128], got ", Q.sizes());
+  const int64_t n = Q.size(0), T = Q.size(1), Hq = Q.size(2);
+  check_kv_cache(op, Kc, Vc, Hq, Kc.dim() == 4 ? Kc.size(2) : 0, Q);
+  const int64_t S_max = Kc.size(1), Hkv = Kc.size(2);
+  check_index(op, "slot_ids", slot_ids, n, Q);
+  check_index(op, "q_start", q_start, n, Q);
+  TORCH_CHECK(T >= 2, op, ": T = ", T,
+              " must be at least 2 (one token is attn_decode's)");
+  TORCH_CHECK(T * (Hq / Hkv) <= VERIFY_MAX_COLS, op, ": T * (Hq / Hkv) = ",
+              T * (Hq / Hkv), " exceeds ", VERIFY_MAX_COLS,
+              " (the tokens of a group's q heads are two MFMA tiles)");
+  TORCH_CHECK(T <= S_max, op, ": T = ", T, " exceeds the cache's S_max = ",
+              S_max);
+  const int R = check_gqa(op, n, Hq, Hkv, S_max, split_rows);
+  TORCH_CHECK(n * T * Hq <= std::numeric_limits<int>::max(), op,
+              ": n * T * Hq = ", n * T * Hq, " exceeds 2^31 - 1");
+  const int64_t splits = (S_max + R - 1) / R;
+  auto O = torch::empty_like(Q);
+  if (n == 0) return O;
+  torch::Tensor Ow, MLw;
+  if (splits > 1) {
+    auto f32 = Q.options().dtype(at::kFloat);
+    Ow = torch::empty({n, T, Hq, splits, (int64_t)ATT_D}, f32);
+    MLw = torch::empty({n, T, Hq, splits, 2}, f32);
+  }
+  attn_verify_launch(Q.data_ptr(), Kc.data_ptr(), Vc.data_ptr(), O.data_ptr(),
+                     splits > 1 ? Ow.data_ptr() : nullptr,
+                     splits > 1 ? MLw.data_ptr() : nullptr,
+                     slot_ids.data_ptr<int>(), q_start.data_ptr<int>(), (int)n,
+                     (int)T, (int)S_max, (int)Hq, (int)Hkv, R, (int)splits,
+                     (float)scale, cur_stream());
   return O;
 }
 
@@ -1609,6 +1653,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kv_lens"), py::arg("slot_ids"), py::arg("Hq"),
         py::arg("Hkv"), py::arg("scale"), py::arg("split_rows") = -1);
   m.attr("DECODE_SPLIT_ROWS") = (int)kDecodeSplitRows;
+  m.def("attn_verify", &attn_verify, py::arg("Q"), py::arg("Kc"),
+        py::arg("Vc"), py::arg("slot_ids"), py::arg("q_start"),
+        py::arg("scale"), py::arg("split_rows") = -1);
+  m.attr("VERIFY_MAX_COLS") = (int)VERIFY_MAX_COLS;
   m.def("skinny_gemm_fp8_norm", &skinny_gemm_fp8_norm);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);

@@ -33,6 +33,12 @@ sequence's token ids by position in ``hist`` and ops.penalize_logits
 logits that the sampler or the argmax reads, inside the decode graph and
 in the eager steps alike.  Log-probabilities keep describing the raw
 logits.
+
+With ``speculative`` = K > 0, a step of greedy requests drafts K tokens
+per sequence (serve/speculative.py: prompt lookup, or ``drafter``) and
+verifies K + 1 in one forward over the decode GEMMs and the multi-token
+attention kernel (ops.attn_verify; docs/KERNELS.md "Multi-token verify
+attention"); the tokens are those of token-by-token greedy decode.
 """
 from __future__ import annotations
 
@@ -52,12 +58,13 @@ import torch.distributed as dist
 from skypilot_amd import ops
 from skypilot_amd.models.llama import build_model
 from skypilot_amd.serve.kv_cache import KV_DTYPES, KVCache
+from skypilot_amd.serve.speculative import accept, ngram_draft, pad_draft
 
 
 @dataclass
 class InferenceContext:
     cache: KVCache
-    mode: str  # "prefill" | "decode" | "append"
+    mode: str  # "prefill" | "decode" | "append" | "verify"
     prefill_slot: int = -1
     prefill_len: int = 0
     # batched prefill: one row per new sequence (all rows share
@@ -87,6 +94,12 @@ class InferenceContext:
     kv_write_idx: Optional[tuple] = None
     # decode: "per_head" or "grouped" (Engine(decode_attn=...))
     decode_attn: str = "per_head"
+    # verify (speculative decoding): tokens [n, verify_t]; row b * T + t is
+    # the token at position verify_start[b] + t.  verify_start int32 [n]
+    # (slot_ids_i32 holds the [n] slots), verify_row_slots int32 [n * T].
+    verify_t: int = 0
+    verify_start: Optional[torch.Tensor] = None
+    verify_row_slots: Optional[torch.Tensor] = None
 
 
 DECODE_ATTN = ("per_head", "grouped")
@@ -150,7 +163,25 @@ class Engine:
                  prefill_chunk: Optional[int] = None,
                  device_sampling: bool = False,
                  kv_dtype: str = "bf16", max_logprobs: int = 0,
-                 decode_attn: str = "per_head", penalties: bool = False):
+                 decode_attn: str = "per_head", penalties: bool = False,
+                 speculative: int = 0, drafter=None):
+        # Speculative decoding: K > 0 drafts K tokens per sequence
+        # (drafter(ids, k) -> list, ngram_draft by default) and verifies
+        # K + 1 in one forward (_verify_step); 0 keeps every path, graph
+        # and staged block as they are.
+        if (isinstance(speculative, bool) or not isinstance(speculative, int)
+                or not 0 <= speculative <= 7):
+            raise ValueError(
+                f"speculative must be an int in [0, 7], got {speculative!r}")
+        if speculative and kv_dtype == "fp8":
+            raise ValueError(
+                "speculative decoding does not serve the fp8 KV cache")
+        if speculative and tp_world > 1:
+            raise ValueError(
+                "speculative decoding does not serve tensor-parallel models")
+        self.speculative = speculative
+        self.drafter = drafter if drafter is not None else ngram_draft
+        self._verify_graphs: Dict[int, tuple] = {}
         # False keeps the decode graph, the staged block and every code
         # path as they are without the feature, and submit() rejects a
         # request that sets a penalty.
@@ -221,6 +252,11 @@ class Engine:
             raise ValueError(
                 f'decode_attn="grouped" takes at most {ops.GQA_MAX_GROUP} q '
                 f"heads per kv head, the model has {group}")
+        if speculative and (speculative + 1) * group > ops.VERIFY_MAX_COLS:
+            raise ValueError(
+                f"speculative = {speculative} needs (K + 1) * group = "
+                f"{(speculative + 1) * group} columns, the verify kernel "
+                f"takes {ops.VERIFY_MAX_COLS}")
         self.max_seq = min(max_seq, self.cfg.max_seq_len)
         if max_batch is None:
             if hbm_budget_gb is None:
@@ -245,7 +281,8 @@ class Engine:
         self._stop = threading.Event()
         self._thread: Optional[threading.Thread] = None
         self.stats = {"requests": 0, "tokens_generated": 0,
-                      "prefill_tokens": 0, "graph_buckets": []}
+                      "prefill_tokens": 0, "graph_buckets": [],
+                      "spec_steps": 0, "spec_drafted": 0, "spec_accepted": 0}
         # hipGraph decode: the whole decode forward (~7 kernels/layer +
         # head = ~230 launches for 8B) replays as ONE graph launch per
         # power-of-two batch bucket.  Low-concurrency decode is
@@ -934,6 +971,119 @@ class Engine:
             self.stats["tokens_generated"] += 1
             self._maybe_finish(slot, req, next_id)
 
+    # ----------------------- speculative decoding ----------------------
+    def _verify_forward(self, toks, start, slots):
+        """The verify forward and its argmax: toks int [b, T], start and
+        slots int32 [b] device tensors -> token ids [b, T] (ties to the
+        lowest index, as decode_advance has them).  Captured once per
+        bucket with use_graphs, run as it is in eager mode."""
+        b, T = toks.shape
+        positions = (start[:, None] + torch.arange(
+            T, dtype=torch.int32, device=self.device)[None, :]).reshape(-1)
+        ctx = InferenceContext(
+            cache=self.cache, mode="verify", slot_ids_i32=slots,
+            verify_t=T, verify_start=start,
+            verify_row_slots=slots[:, None].repeat(1, T).reshape(-1))
+        return self.model(toks.long(), positions, ctx).argmax(-1)
+
+    def _get_verify_graph(self, b: int):
+        """Lazily capture _verify_forward for batch bucket `b`.  The step's
+        inputs travel as one pinned-host -> device copy of an int32
+        [T + 2, b] block: rows 0..T-1 the token rows, row T q_start, row
+        T + 1 the slot.  Padding rows verify zeros at the start of the
+        scratch slot."""
+        if b in self._verify_graphs:
+            return self._verify_graphs[b]
+        T = self.speculative + 1
+        st = {
+            "host": torch.zeros(T + 2, b, dtype=torch.int32,
+                                pin_memory=True),
+            "block": torch.zeros(T + 2, b, dtype=torch.int32,
+                                 device=self.device),
+        }
+        st["block"][T + 1] = self._scratch_slot
+
+        def run():
+            blk = st["block"]
+            return self._verify_forward(blk[:T].t(), blk[T], blk[T + 1])
+
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):  # warmup on a side stream, as _get_graph
+                run()
+        torch.cuda.current_stream().wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            st["ids"] = run()
+        self._verify_graphs[b] = (g, st)
+        self.stats["spec_graph_buckets"] = sorted(self._verify_graphs)
+        return self._verify_graphs[b]
+
+    @torch.no_grad()
+    def _verify_step(self) -> bool:
+        """One speculative step for every active sequence, or False when
+        the step has to be an ordinary _decode_step: a request that
+        samples, sets a penalty or wants log-probabilities, work pending
+        or prefilling, a sequence within K + 1 rows of max_seq - 1, or no
+        draft at all."""
+        K = self.speculative
+        slots = sorted(self.active.keys())
+        reqs = [self.active[s] for s in slots]
+        if (not slots or not self.pending.empty() or self.prefilling
+                or any(r.temperature != 0 or r.logprobs is not None
+                       or self._pen_row(r)[:3] != (0.0, 0.0, 1.0)
+                       for r in reqs)):
+            return False
+        lens = [self.cache.lens[s] for s in slots]
+        if any(l + K + 1 > self.max_seq - 1 for l in lens):
+            return False
+        drafts = [list(self.drafter(r.prompt_ids + r.out_ids, K))[:K]
+                  for r in reqs]
+        if not any(drafts):
+            return False
+        n, T = len(slots), K + 1
+        rows = [[r.out_ids[-1]] + pad_draft(d, K, r.out_ids[-1])
+                for r, d in zip(reqs, drafts)]
+        if self.use_graphs:
+            g, st = self._get_verify_graph(self._bucket(n))
+            h = st["host"].numpy()
+            h[:T, :n] = list(zip(*rows))
+            h[:T + 1, n:] = 0
+            h[T, :n] = lens
+            h[T + 1, :n] = slots
+            h[T + 1, n:] = self._scratch_slot
+            st["block"].copy_(st["host"], non_blocking=True)
+            g.replay()
+            ids = st["ids"][:n].tolist()  # the step's one sync
+        else:
+            def i32(vals):
+                return torch.tensor(vals, dtype=torch.int32,
+                                    device=self.device)
+            ids = self._verify_forward(i32(rows), i32(lens),
+                                       i32(slots)).tolist()
+        self.stats["spec_steps"] += 1
+        for i, (slot, req) in enumerate(zip(slots, reqs)):
+            out = accept(drafts[i], ids[i], req.stop_id,
+                         req.max_tokens - len(req.out_ids))
+            self.stats["spec_drafted"] += len(drafts[i])
+            self.stats["spec_accepted"] += len(out) - 1
+            # Rows past the new length stay in the cache as stale rows.
+            for next_id in out:
+                self.cache.lens[slot] += 1
+                req.out_ids.append(next_id)
+                if req.stream_queue is not None:
+                    req.stream_queue.put(next_id)
+                self.stats["tokens_generated"] += 1
+                self._maybe_finish(slot, req, next_id)
+        return True
+
+    def _step_active(self) -> None:
+        """One step for the active sequences: a verify step where
+        speculative decoding is on and applies, else a decode step."""
+        if not (self.speculative and self._verify_step()):
+            self._decode_step()
+
     def _samp_rows(self, reqs: List[Request]):
         """Per-row (temperature, top_p, top_k, seed) for the device
         sampler — what the TP decode plan carries; None when off."""
@@ -1124,7 +1274,7 @@ class Engine:
                     self._append_step()
                     did = True
                 if self.active:
-                    self._decode_step()
+                    self._step_active()
                     did = True
                 if not did:
                     time.sleep(0.005)
@@ -1142,7 +1292,7 @@ class Engine:
                 self._prefill(batch)
                 did = True
             if self.active:
-                self._decode_step()
+                self._step_active()
                 did = True
             if not did:
                 time.sleep(0.005)

@@ -336,6 +336,11 @@ def build_parser() -> argparse.ArgumentParser:
                          "row once per kv head and splits the kv length "
                          "across blocks (models with at most 16 q heads "
                          "per kv head)")
+    ap.add_argument("--speculative", type=int, default=0, metavar="K",
+                    help="speculative decoding: draft K (0..7) tokens per "
+                         "sequence by prompt lookup and verify K + 1 in one "
+                         "forward; greedy requests only, bf16 KV cache, no "
+                         "--tp; (K + 1) * q heads per kv head <= 32")
     return ap
 
 
@@ -368,7 +373,8 @@ def main():
                         kv_dtype=args.kv_dtype,
                         decode_attn=args.decode_attn,
                         max_logprobs=args.max_logprobs,
-                        penalties=args.penalties)
+                        penalties=args.penalties,
+                        speculative=args.speculative)
         if args.fp8_decode:
             engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         if args.fp4_decode:
@@ -391,7 +397,8 @@ def main():
                     kv_dtype=args.kv_dtype,
                     decode_attn=args.decode_attn,
                     max_logprobs=args.max_logprobs,
-                    penalties=args.penalties)
+                    penalties=args.penalties,
+                    speculative=args.speculative)
     if args.fp8_decode:
         n8 = engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         print(f"fp8 decode weights: {n8} tensors quantized", flush=True)
