@@ -72,6 +72,9 @@ def main():
     ap.add_argument("--fp4-prefill", type=int, default=None, metavar="N",
                     help="MXFP4 weights for prefill too, from N tokens up "
                          "(0: the measured thresholds)")
+    ap.add_argument("--bf16-decode-max-batch", type=int, default=1,
+                    help="largest decode batch served by the bf16 MFMA GEMM "
+                         "(1: off)")
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked prefill: tokens per append forward "
                          "(multiple of 64); default whole-prompt prefill")
@@ -113,6 +116,10 @@ def main():
         n4 = eng.enable_fp4_prefill(args.fp4_prefill or "measured")
         print(f"fp4 prefill weights: {n4} tensors, from "
               f"{args.fp4_prefill or 'measured'} tokens")
+    if args.bf16_decode_max_batch > 1:
+        eng.enable_bf16_mfma_decode(args.bf16_decode_max_batch)
+        print(f"bf16 MFMA decode GEMM up to batch "
+              f"{args.bf16_decode_max_batch}")
     eng.start()
     prompt = list(range(2, 2 + args.prompt_len))
     # warmup

@@ -677,6 +677,73 @@ def _fp8_mfma_class(i: int, o: int) -> str:
     return "wide" if o >= 16384 else "deep" if i > 8192 else "square"
 
 
+# ---- bf16-weight MFMA decode GEMM (docs/KERNELS.md "bf16-weight MFMA decode
+# GEMM"): the model's own bf16 weights, no copy and no registration.
+def skinny_gemm_bf16_mfma(x: torch.Tensor, w: torch.Tensor,
+                          row_tiles: int = 0,
+                          k_splits: int = 0) -> torch.Tensor:
+    """y[n, O] = bf16(sum_k x[n, k] * w[o, k]) for 1 <= n <= 64 tokens,
+    I % 128 == 0, O % 16 == 0, bf16 x and w: the bf16-weight decode GEMM on
+    the matrix cores (skinny_gemm_bf16_mfma.hip), fp32 accumulation.
+    row_tiles (16-row tiles per wave: 1, 2, 4) and k_splits (blocks along K:
+    1, 2, 4, 8) are 0 for the launcher's choice, which depends on (O, I)
+    alone: a token's output bits then do not depend on the batch it is
+    computed in.  Forced values are for tests and the benchmark and may
+    change the bits (k_splits changes the order of the sum)."""
+    if x.is_cuda:
+        C = _require_native("skinny_gemm_bf16_mfma")
+        return C.skinny_gemm_bf16_mfma(x, w, row_tiles, k_splits)
+    return (x.float() @ w.float().t()).bfloat16()
+
+
+# Largest decode batch that plain bf16 weights serve through the MFMA GEMM
+# (opt-in; 1 keeps decode_linear exactly as it was).
+_BF16_MAX_BATCH = 1
+
+
+def set_bf16_decode_max_batch(m: int) -> None:
+    """Let bf16 weights with no fp8 or fp4 entry serve decode batches of
+    2..m tokens through skinny_gemm_bf16_mfma, where the measured route
+    table says it wins.  m in 1..64; 1, the default, turns it off."""
+    global _BF16_MAX_BATCH
+    if not isinstance(m, int) or isinstance(m, bool) or not 1 <= m <= 64:
+        raise ValueError(
+            f"set_bf16_decode_max_batch: m must be an int in 1..64, got {m!r}")
+    _BF16_MAX_BATCH = m
+
+
+# Measured routes for 2 <= n <= _BF16_MAX_BATCH (bench_gemm_bf16_mfma.py on
+# MI355X, docs/BENCHMARKS.md "bf16-weight MFMA decode GEMM"): per shape class
+# (_fp8_mfma_class), the column-tile counts NT = ceil(n/16) at which the
+# kernel beat what decode_linear otherwise runs (the bf16 GEMV or F.linear)
+# on every measured shape and n of the class by more than the larger spread
+# (at most 0.6 %).  Only "deep" at NT = 3 qualifies (1.06x, 1.06x, 1.04x at
+# n = 33, 40, 48, two runs; 1.01x at 64 is left out, 0.92x-0.98x at
+# n <= 32).  "square" wins on o (1.04x-1.42x at n = 4..16, 1.01x at 32) but
+# loses on q|k|v at every n (0.78x-0.93x); "wide" wins on
+# gate|up up to n = 16 (1.10x) but loses on lm_head at every n (0.70x-0.92x).
+_BF16_MFMA_ROUTES = {
+    "wide": (),
+    "deep": (3,),
+    "square": (),
+}
+
+
+def _decode_linear_bf16_mfma(x, weight, n, i, o):
+    """The bf16 MFMA route of decode_linear, or None where it does not
+    apply."""
+    if not (2 <= n <= _BF16_MAX_BATCH and x.is_cuda
+            and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
+            and weight.dim() == 2 and weight.is_contiguous()
+            and i % 128 == 0 and o % 16 == 0
+            and (n + 15) // 16 in _BF16_MFMA_ROUTES[_fp8_mfma_class(i, o)]):
+        return None
+    x2 = x.reshape(n, i).contiguous()
+    if x2.data_ptr() % 16 or weight.data_ptr() % 16:
+        return None
+    return skinny_gemm_bf16_mfma(x2, weight)
+
+
 # ---- MXFP4 decode weights (docs/KERNELS.md "MXFP4-weight MFMA decode GEMM")
 # OCP MXFP4: e2m1 codes in blocks of 32 along K with one E8M0 exponent byte
 # per block, 4.25 bits per weight.  The two functions below are the
@@ -968,6 +1035,13 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
             C = _require_native("skinny_gemm_fp8")
             y = C.skinny_gemm_fp8(x.reshape(n, i).contiguous(), ent[0],
                                   ent[1])
+            return y.view(*lead, o)
+    # Plain bf16 weights at 2 <= n <= set_bf16_decode_max_batch(m) (default
+    # 1: never) take the bf16 MFMA GEMM where _BF16_MFMA_ROUTES has it
+    # beating what follows.
+    if _BF16_MAX_BATCH >= 2:
+        y = _decode_linear_bf16_mfma(x, weight, n, i, o)
+        if y is not None:
             return y.view(*lead, o)
     if (use_native and x.is_cuda and x.dtype == torch.bfloat16
             and 1 <= n <= 8 and i % 512 == 0):
@@ -1528,6 +1602,7 @@ __all__ = [
     "attn_decode_qkv_gqa", "attn_decode_qkv_gqa_fp8",
     "attn_verify", "VERIFY_MAX_COLS",
     "skinny_gemm_fp8_mfma", "set_fp8_decode_max_batch",
+    "skinny_gemm_bf16_mfma", "set_bf16_decode_max_batch",
     "quantize_mxfp4", "dequantize_mxfp4", "skinny_gemm_fp4_mfma",
     "register_fp4_weight", "clear_fp4_weights", "set_fp4_decode_max_batch",
     "quantize_mxfp8", "dequantize_mxfp8", "quantize_mxfp8_rows",

@@ -16,6 +16,7 @@
 #include "attn_verify.h"
 #include "attn_launch.h"
 #include "kv_fp8_launch.h"
+#include "skinny_gemm_bf16_mfma.h"
 
 #define CHECK_GPU(x) TORCH_CHECK(x.is_cuda(), #x " must be on GPU")
 #define CHECK_CONTIG(x) TORCH_CHECK(x.is_contiguous(), #x " must be contiguous")
@@ -1127,6 +1128,52 @@ torch::Tensor skinny_gemm_fp4_mfma(torch::Tensor X, torch::Tensor codes,
   return y;
 }
 
+torch::Tensor skinny_gemm_bf16_mfma(torch::Tensor X, torch::Tensor W,
+                                    int64_t row_tiles, int64_t k_splits) {
+  // Y[N,O] = X[N,I] @ W[O,I]^T over the bf16 weight itself, N up to 64
+  // (skinny_gemm_bf16_mfma.hip).  row_tiles (1, 2, 4) and k_splits (1, 2, 4,
+  // 8): 0 = the launcher's choice from (O, I); forced values may change the
+  // output bits (they change the k order).
+  const char* op = "skinny_gemm_bf16_mfma";
+  TORCH_CHECK(row_tiles == 0 || row_tiles == 1 || row_tiles == 2 ||
+                  row_tiles == 4,
+              op, ": row_tiles must be 0, 1, 2 or 4, got ", row_tiles);
+  TORCH_CHECK(k_splits == 0 || k_splits == 1 || k_splits == 2 ||
+                  k_splits == 4 || k_splits == 8,
+              op, ": k_splits must be 0, 1, 2, 4 or 8, got ", k_splits);
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(N >= 1 && N <= 64, op, ": N must be 1..64, got ", N);
+  TORCH_CHECK(I >= 128 && I % 128 == 0 &&
+                  I <= std::numeric_limits<int>::max(),
+              op, ": I must be a positive multiple of 128, got ", I);
+  check_dense(op, "W", W, at::kBFloat16, X);
+  TORCH_CHECK(W.dim() == 2 && W.size(1) == I, op,
+              ": W must be [O, I] with I = ", I, ", got ", W.sizes());
+  const int64_t O = W.size(0);
+  // n * O fits an int in the combine kernel
+  TORCH_CHECK(O >= 16 && O % 16 == 0 &&
+                  O <= std::numeric_limits<int>::max() / 64,
+              op, ": O must be a positive multiple of 16, got ", O);
+  int tr = (int)row_tiles, ks = (int)k_splits;
+  skinny_gemm_bf16_mfma_plan((int)I, (int)O, &tr, &ks);
+  auto y = torch::empty({N, O}, X.options());
+  // fp32 partials of the k splits, from the caching allocator, live for
+  // the call; every element the combine kernel reads is written first.
+  torch::Tensor part;
+  if (ks > 1) part = torch::empty({ks, N, O}, X.options().dtype(at::kFloat));
+  const torch::Tensor* ts[] = {&X, &W, &y};
+  const char* names[] = {"X", "W", "the output"};
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(aligned16(*ts[i]), op, ": ", names[i],
+                " must start on a 16-byte boundary");
+  skinny_gemm_bf16_mfma_launch(W.data_ptr(), X.data_ptr(), y.data_ptr(),
+                               ks > 1 ? part.data_ptr<float>() : nullptr,
+                               (int)N, (int)I, (int)O, tr, ks, cur_stream());
+  return y;
+}
+
 // X [N, I] bf16 -> MXFP8 (gemm_mxfp4_a8.hip): codes uint8 [N_pad, I] e4m3fn,
 // exps uint8 [N_pad, I/32], N_pad = N rounded up to the GEMM's token tile of
 // 128; rows N..N_pad-1 are zero codes with exponent 127.
@@ -1617,6 +1664,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w8"), py::arg("scale"), py::arg("row_tiles") = 0);
   m.def("skinny_gemm_fp4_mfma", &skinny_gemm_fp4_mfma, py::arg("x"),
         py::arg("codes"), py::arg("exps"), py::arg("row_tiles") = 0);
+  m.def("skinny_gemm_bf16_mfma", &skinny_gemm_bf16_mfma, py::arg("x"),
+        py::arg("w"), py::arg("row_tiles") = 0, py::arg("k_splits") = 0);
   m.def("quantize_mxfp8_rows", &quantize_mxfp8_rows, py::arg("x"));
   m.def("gemm_mxfp4_a8", &gemm_mxfp4_a8, py::arg("x"), py::arg("codes"),
         py::arg("exps"));

@@ -365,6 +365,14 @@ class Engine:
         _ops.set_fp4_prefill(min_tokens)
         return self._fp4_registered
 
+    def enable_bf16_mfma_decode(self, max_batch: int = 64) -> None:
+        """Route decode batches of 2..max_batch tokens over plain bf16
+        weights through the bf16 MFMA GEMM where its measured table has it
+        winning (ops.set_bf16_decode_max_batch).  It changes no weights, and
+        tensors registered as fp8 or fp4 keep their own routes."""
+        from skypilot_amd import ops as _ops
+        _ops.set_bf16_decode_max_batch(max_batch)
+
     def _claim_decode_weights(self, fmt: str) -> None:
         have = getattr(self, "_decode_weight_format", fmt)
         if have != fmt:

@@ -322,6 +322,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "GEMM) where the measured table has it winning "
                          "(docs/BENCHMARKS.md: nowhere yet); not with "
                          "--fp8-decode or --tp")
+    ap.add_argument("--bf16-decode-max-batch", type=int, default=1,
+                    help="largest decode batch that plain bf16 weights "
+                         "serve through the bf16 MFMA GEMM where its "
+                         "measured table has it winning (1..64; 1: off)")
     ap.add_argument("--tp", type=int, default=1,
                     help="tensor-parallel degree; run under torchrun "
                          "with one rank per GPU (70B serving: --tp 8)")
@@ -379,6 +383,8 @@ def main():
             engine.enable_fp8_decode(max_batch=args.fp8_decode_max_batch)
         if args.fp4_decode:
             engine.enable_fp4_decode(max_batch=args.fp4_decode_max_batch)
+        if args.bf16_decode_max_batch > 1:
+            engine.enable_bf16_mfma_decode(args.bf16_decode_max_batch)
         if rank > 0:
             engine.follower_loop()
             return
@@ -408,6 +414,8 @@ def main():
     if args.fp4_prefill:
         n4 = engine.enable_fp4_prefill()
         print(f"fp4 prefill weights: {n4} tensors quantized", flush=True)
+    if args.bf16_decode_max_batch > 1:
+        engine.enable_bf16_mfma_decode(args.bf16_decode_max_batch)
     engine.start()
     app = create_app(engine, args.model)
     print(f"serving {args.model} on {args.host}:{args.port} "
