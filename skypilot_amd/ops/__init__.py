@@ -352,6 +352,10 @@ def linear(x, w, b=None, route: int = -1):
         y = _prefill_linear_fp4(x, w, b)
         if y is not None:
             return y
+    if _FP8_PREFILL is not None and not torch.is_grad_enabled():
+        y = _prefill_linear_fp8(x, w, b)
+        if y is not None:
+            return y
     _require_native("linear")
     return _LinearFn.apply(x, w, b, route)
 
@@ -396,7 +400,8 @@ def qkv_linear(x, wq, wk, wv, bq=None, bk=None, bv=None, route: int = -1):
     if not (x.is_cuda and x.dtype == torch.bfloat16
             and wq.dtype == torch.bfloat16):
         return lin(x, wq, bq), lin(x, wk, bk), lin(x, wv, bv)
-    if _FP4_PREFILL is not None and not torch.is_grad_enabled():
+    if ((_FP4_PREFILL is not None or _FP8_PREFILL is not None)
+            and not torch.is_grad_enabled()):
         # three calls; a projection the route does not take is F.linear's
         return tuple(linear(x, w, b, route)
                      for w, b in ((wq, bq), (wk, bk), (wv, bv)))
@@ -675,6 +680,94 @@ _FP8_MFMA_ROUTES = {
 
 def _fp8_mfma_class(i: int, o: int) -> str:
     return "wide" if o >= 16384 else "deep" if i > 8192 else "square"
+
+
+# ---- fp8-weight GEMM beyond 64 tokens (docs/KERNELS.md "FP8-weight GEMM for
+# any token count"): prefill, prompt chunks, verify steps and decode batches
+# above 64 from the registered fp8 weights.
+def gemm_fp8_w8(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
+                row_tiles: int = 0) -> torch.Tensor:
+    """y[n, O] = bf16(scale[o] * sum_k x[n, k] * e4m3(w8[o, k])) for any
+    n >= 1, I % 128 == 0, O % 64 == 0: skinny_gemm_fp8_mfma's product with
+    the x tile shared by a block's waves through LDS (gemm_fp8_w8.hip).  A
+    token's output bits do not depend on the batch it is computed in, nor on
+    row_tiles (16-row tiles per wave: 0 the launcher's choice; 1, 2 for the
+    benchmark)."""
+    if x.is_cuda:
+        return _require_native("gemm_fp8_w8").gemm_fp8_w8(x, w8, scale,
+                                                          row_tiles)
+    w = w8.view(torch.float8_e4m3fn).float() * scale[:, None]
+    return (x.float() @ w.t()).to(torch.bfloat16)
+
+
+# Smallest token count that ops.linear / ops.qkv_linear, and decode_linear
+# above 64 rows, serve from registered fp8 weights through gemm_fp8_w8: None
+# is off, an int one threshold for every shape, "measured" the table below.
+_FP8_PREFILL = None
+
+# Measured routes per shape class (_fp8_mfma_class), from
+# bench_gemm_fp8_prefill.py on MI355X (docs/BENCHMARKS.md "FP8-weight GEMM
+# beyond 64 tokens"): the inclusive token ranges (lo, hi) in which the kernel
+# beat F.linear on the bf16 weight on every measured shape of the class by
+# more than the spread of the repeats (at most 1.2 %).  A class with no range
+# is not routed under "measured".  "wide" (gate|up) wins inside one token tile:
+# 1.09x, 1.06x, 1.06x at n = 65, 96, 128; from 192 up a second wave of blocks
+# costs more than the halved W stream saves (0.81x-0.88x at 192, 256, 0.59x-
+# 0.63x at 512, 2048).  "square" and "deep" lose: their grids of 64..96
+# blocks leave most of the 256 CUs idle (q|k|v 0.60x-0.90x but 1.07x at 256,
+# o 0.44x-0.88x, down 0.40x-0.87x).
+_FP8_PREFILL_ROUTES = {
+    "wide": ((65, 128),),
+    "deep": (),
+    "square": (),
+}
+
+
+def set_fp8_prefill(min_tokens) -> None:
+    """Route ops.linear and ops.qkv_linear, and ops.decode_linear above 64
+    rows, through gemm_fp8_w8 for weights registered as fp8, from min_tokens
+    tokens up, when autograd is off.  None (the default) turns the route off,
+    an int >= 1 forces it from that count, "measured" takes the per-class
+    token ranges of _FP8_PREFILL_ROUTES."""
+    global _FP8_PREFILL
+    ok = (min_tokens is None or min_tokens == "measured"
+          or (isinstance(min_tokens, int) and not isinstance(min_tokens, bool)
+              and min_tokens >= 1))
+    if not ok:
+        raise ValueError("set_fp8_prefill: min_tokens must be None, "
+                         f"'measured' or an int >= 1, got {min_tokens!r}")
+    _FP8_PREFILL = min_tokens
+
+
+def _prefill_gemm_fp8(x, w, n, i, o):
+    """gemm_fp8_w8 on w's registered fp8 copy for a bf16 GPU x of n rows, or
+    None where the route does not apply."""
+    # the vocabulary projection (O >= 100k, as decode_linear tells it) stays
+    # on bf16: it is not among the measured shapes
+    if i % 128 or o % 64 or o >= 100_000:
+        return None
+    if _FP8_PREFILL == "measured":
+        if not any(lo <= n <= hi
+                   for lo, hi in _FP8_PREFILL_ROUTES[_fp8_mfma_class(i, o)]):
+            return None
+    elif n < _FP8_PREFILL:
+        return None
+    ent = _FP8_WEIGHTS.get(w.data_ptr())
+    # data_ptr can be recycled after a free; require matching shape
+    if ent is None or tuple(ent[0].shape) != (o, i):
+        return None
+    return gemm_fp8_w8(x.reshape(n, i).contiguous(), ent[0], ent[1])
+
+
+def _prefill_linear_fp8(x, w, b):
+    """The fp8 route of linear for a bf16 GPU x, or None where it does not
+    apply."""
+    o, i = w.shape
+    y = _prefill_gemm_fp8(x, w, x.numel() // i, i, o)
+    if y is None:
+        return None
+    y = y.view(*x.shape[:-1], o)
+    return y if b is None else y + b
 
 
 # ---- bf16-weight MFMA decode GEMM (docs/KERNELS.md "bf16-weight MFMA decode
@@ -1001,6 +1094,13 @@ def decode_linear(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     # below changes.
     if _FP4_WEIGHTS:
         y = _decode_linear_fp4(x, weight, n, i, o)
+        if y is not None:
+            return y.view(*lead, o)
+    # Above 64 rows (verify steps, big decode batches) registered fp8 weights
+    # serve through gemm_fp8_w8 where set_fp8_prefill routes the count.
+    if (_FP8_PREFILL is not None and n > 64 and _FP8_WEIGHTS and x.is_cuda
+            and x.dtype == torch.bfloat16 and not torch.is_grad_enabled()):
+        y = _prefill_gemm_fp8(x, weight, n, i, o)
         if y is not None:
             return y.view(*lead, o)
     wbytes = 2 * i * o
@@ -1607,4 +1707,5 @@ __all__ = [
     "register_fp4_weight", "clear_fp4_weights", "set_fp4_decode_max_batch",
     "quantize_mxfp8", "dequantize_mxfp8", "quantize_mxfp8_rows",
     "gemm_mxfp4_a8", "set_fp4_prefill",
+    "gemm_fp8_w8", "set_fp8_prefill",
 ]

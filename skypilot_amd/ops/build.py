@@ -39,6 +39,7 @@ HIP_SOURCES = [
     "skinny_gemm_fp4_mfma.hip",
     "skinny_gemm_bf16_mfma.hip",
     "gemm_mxfp4_a8.hip",
+    "gemm_fp8_w8.hip",
     "wgrad_gemm.hip",
     "decode_fused.hip",
     "decode_sample.hip",
@@ -47,7 +48,7 @@ HIP_SOURCES = [
 ]
 CPP_SOURCES = ["bindings.cpp"]
 # Extra flags per device TU.  The grouped decode and verify kernels, the fp8, fp4 and
-# bf16 MFMA decode GEMMs and the MXFP4 x MXFP8 prefill GEMM are built without packed-fp32 instructions (v_pk_mul_f32 and
+# bf16 MFMA decode GEMMs, the MXFP4 x MXFP8 prefill GEMM and the fp8-weight GEMM are built without packed-fp32 instructions (v_pk_mul_f32 and
 # kin): their fp32 vector math is then plain scalar-lane VALU code whatever
 # the optimiser would pick.
 _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
@@ -58,6 +59,7 @@ EXTRA_FLAGS = {
     "skinny_gemm_fp4_mfma.hip": _NO_PK_F32,
     "skinny_gemm_bf16_mfma.hip": _NO_PK_F32,
     "gemm_mxfp4_a8.hip": _NO_PK_F32,
+    "gemm_fp8_w8.hip": _NO_PK_F32,
 }
 
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

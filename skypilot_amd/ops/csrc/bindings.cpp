@@ -58,6 +58,8 @@ void quantize_mxfp8_rows_launch(const void*, void*, void*, int, int, int,
                                 hipStream_t);
 void gemm_mxfp4_a8_launch(const void*, const void*, const void*, const void*,
                           void*, int, int, int, int, hipStream_t);
+void gemm_fp8_w8_launch(const void*, const float*, const void*, void*, int,
+                        int, int, int, hipStream_t);
 void gemm_nt_launch(const void*, const void*, void*, int, int, long long,
                     hipStream_t);
 void adamw_mt_launch(const void*, const void*, const void*, const void*,
@@ -1241,6 +1243,37 @@ torch::Tensor gemm_mxfp4_a8(torch::Tensor X, torch::Tensor codes,
   return y;
 }
 
+torch::Tensor gemm_fp8_w8(torch::Tensor X, torch::Tensor W8,
+                          torch::Tensor scale, int64_t row_tiles) {
+  // skinny_gemm_fp8_mfma's product for any N >= 1 (gemm_fp8_w8.hip): the X
+  // tile is shared by a block's waves through LDS.  row_tiles: 0 = the
+  // launcher's choice; 1 or 2 force the row tiles per wave (same bits).
+  const char* op = "gemm_fp8_w8";
+  TORCH_CHECK(row_tiles == 0 || row_tiles == 1 || row_tiles == 2, op,
+              ": row_tiles must be 0, 1 or 2, got ", row_tiles);
+  check_dense(op, "X", X, at::kBFloat16, X);
+  TORCH_CHECK(X.dim() == 2, op, ": X must be [N, I], got ", X.sizes());
+  const int64_t N = X.size(0), I = X.size(1);
+  TORCH_CHECK(N >= 1 && N <= 65535 * 128, op, ": N must be 1..",
+              65535 * 128, ", got ", N);
+  TORCH_CHECK(I >= 128 && I % 128 == 0 &&
+                  I <= std::numeric_limits<int>::max(),
+              op, ": I must be a positive multiple of 128, got ", I);
+  check_fp8_weight(op, W8, scale, I, X);
+  const int64_t O = W8.size(0);
+  TORCH_CHECK(O % 64 == 0, op, ": O must be a multiple of 64, got ", O);
+  auto y = torch::empty({N, O}, X.options());
+  const torch::Tensor* ts[] = {&X, &W8, &scale, &y};
+  const char* names[] = {"X", "W8", "scale", "the output"};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(aligned16(*ts[i]), op, ": ", names[i],
+                " must start on a 16-byte boundary");
+  gemm_fp8_w8_launch(W8.data_ptr(), scale.data_ptr<float>(), X.data_ptr(),
+                     y.data_ptr(), (int)N, (int)I, (int)O, (int)row_tiles,
+                     cur_stream());
+  return y;
+}
+
 torch::Tensor skinny_gemm(torch::Tensor X, torch::Tensor W) {
   // Y[N,O] = X[N,I] @ W[O,I]^T (decode GEMV; see skinny_gemm.hip)
   CHECK_GPU(X); CHECK_CONTIG(X); CHECK_BF16(X);
@@ -1669,6 +1702,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("quantize_mxfp8_rows", &quantize_mxfp8_rows, py::arg("x"));
   m.def("gemm_mxfp4_a8", &gemm_mxfp4_a8, py::arg("x"), py::arg("codes"),
         py::arg("exps"));
+  m.def("gemm_fp8_w8", &gemm_fp8_w8, py::arg("x"), py::arg("w8"),
+        py::arg("scale"), py::arg("row_tiles") = 0);
   m.def("transpose_bf16", &transpose_bf16);
   m.def("gemm_nt", &gemm_nt);
   m.def("wgrad_tn", &wgrad_tn);

@@ -326,8 +326,29 @@ class Engine:
         from skypilot_amd import ops as _ops
         self._claim_decode_weights("fp8")
         _ops.set_fp8_decode_max_batch(max_batch)
-        return self._register_decode_weights(_ops.register_fp8_weight,
-                                             min_bytes, 1024)
+        self._fp8_registered = self._register_decode_weights(
+            _ops.register_fp8_weight, min_bytes, 1024)
+        return self._fp8_registered
+
+    def enable_fp8_prefill(self, min_tokens="measured",
+                           min_bytes: int = 1 << 20) -> int:
+        """Serve prefill, prompt chunks, verify steps and decode batches of
+        at least min_tokens tokens (decode_linear: above 64 rows) from the
+        row-wise fp8 weights too: ops.linear, ops.qkv_linear and
+        ops.decode_linear run ops.gemm_fp8_w8 (ops.set_fp8_prefill).
+        "measured" takes the per-shape token ranges of the benchmark, an int
+        forces one threshold.  Registers the fp8 weights if enable_fp8_decode
+        has not (every large linear weight with I % 128 == 0; decode steps
+        then read the ones their kernels accept as well).  lm_head's prefill
+        GEMM, training and the tensor-parallel model keep bf16.  Returns the
+        number of weights registered."""
+        from skypilot_amd import ops as _ops
+        self._claim_decode_weights("fp8")
+        if getattr(self, "_fp8_registered", None) is None:
+            self._fp8_registered = self._register_decode_weights(
+                _ops.register_fp8_weight, min_bytes, 128)
+        _ops.set_fp8_prefill(min_tokens)
+        return self._fp8_registered
 
     def enable_fp4_decode(self, min_bytes: int = 1 << 20,
                           max_batch: int = 64) -> int:

@@ -322,6 +322,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "GEMM) where the measured table has it winning "
                          "(docs/BENCHMARKS.md: nowhere yet); not with "
                          "--fp8-decode or --tp")
+    ap.add_argument("--fp8-prefill", action="store_true",
+                    help="serve prefill, prompt chunks, verify steps and "
+                         "decode batches above 64 tokens from the row-wise "
+                         "fp8 weights too (bf16 activations, LDS-shared MFMA "
+                         "GEMM) where the measured table has it winning "
+                         "(docs/BENCHMARKS.md); not with --fp4-decode or --tp")
     ap.add_argument("--bf16-decode-max-batch", type=int, default=1,
                     help="largest decode batch that plain bf16 weights "
                          "serve through the bf16 MFMA GEMM where its "
@@ -414,6 +420,9 @@ def main():
     if args.fp4_prefill:
         n4 = engine.enable_fp4_prefill()
         print(f"fp4 prefill weights: {n4} tensors quantized", flush=True)
+    if args.fp8_prefill:
+        n8 = engine.enable_fp8_prefill()
+        print(f"fp8 prefill weights: {n8} tensors quantized", flush=True)
     if args.bf16_decode_max_batch > 1:
         engine.enable_bf16_mfma_decode(args.bf16_decode_max_batch)
     engine.start()
