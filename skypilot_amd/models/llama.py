@@ -261,9 +261,13 @@ class MLP(nn.Module):
 
     def forward(self, x, infer_ctx=None):
         decode = infer_ctx is not None and infer_ctx.mode == "decode"
-        lin = ops.decode_linear if decode else ops.linear
-        return lin(ops.swiglu(lin(x, self.w_gate_up.weight)),
-                   self.w_down.weight)
+        if decode:
+            return self.down_from_gu(
+                ops.decode_linear(x, self.w_gate_up.weight))
+        # linear + swiglu, whose backward hands the gate|up weight gradient
+        # its transposed operand (ops.linear_swiglu)
+        return ops.linear(ops.linear_swiglu(x, self.w_gate_up.weight),
+                          self.w_down.weight)
 
     def down_from_gu(self, gu):
         """Decode path with a precomputed (norm-fused) gate_up GEMV."""

@@ -276,9 +276,15 @@ def fused_cross_entropy(logits, targets, ignore_index: int = -100):
 
 
 class _SwiGLUFn(torch.autograd.Function):
+    # `producer`: the _LinearFn node whose output gu is (linear_swiglu), or
+    # None.  Its weight gradient wants dgu transposed on routes 1 and 2, and
+    # the backward kernel can write that copy from the registers that hold
+    # dgu (swiglu_bwd_t), so the producer's linear_wgrad need not read dgu
+    # again to transpose it.
     @staticmethod
-    def forward(ctx, gu):
+    def forward(ctx, gu, producer):
         ctx.save_for_backward(gu)
+        ctx.producer = producer
         if gu.is_cuda:
             C = _require_native("swiglu")
             return C.swiglu_fwd(gu.contiguous())
@@ -291,7 +297,21 @@ class _SwiGLUFn(torch.autograd.Function):
         (gu,) = ctx.saved_tensors
         if gu.is_cuda:
             C = native()
-            return C.swiglu_bwd(gu.contiguous(), dy.contiguous())
+            node = ctx.producer
+            M2 = gu.shape[-1]
+            rows = gu.numel() // M2
+            if (node is not None and node.needs_input_grad[1]
+                    and rows % 64 == 0 and M2 % 128 == 0
+                    and node.in_features % 64 == 0):
+                route = node.route
+                if route < 0:
+                    route = C.wgrad_route(rows, M2, node.in_features)
+                if route in (1, 2):
+                    dgu, node.dyT = C.swiglu_bwd_t(
+                        gu.contiguous().view(rows, M2),
+                        dy.contiguous().view(rows, M2 // 2))
+                    return dgu.view(gu.shape), None
+            return C.swiglu_bwd(gu.contiguous(), dy.contiguous()), None
         M = gu.shape[-1] // 2
         g, u = gu.float().split(M, dim=-1)
         dyf = dy.float()
@@ -299,13 +319,13 @@ class _SwiGLUFn(torch.autograd.Function):
         silu = g * sg
         dg = dyf * u * (sg + silu * (1 - sg))
         du = dyf * silu
-        return torch.cat([dg, du], dim=-1).to(gu.dtype)
+        return torch.cat([dg, du], dim=-1).to(gu.dtype), None
 
 
 def swiglu(gu):
     """Fused silu(gate) * up over a fused [.., 2M] gate|up tensor.  On
     GPU M must be a multiple of 8 (16-byte vectors); other widths raise."""
-    return _SwiGLUFn.apply(gu)
+    return _SwiGLUFn.apply(gu, None)
 
 
 # ---- linear layers of the training path -----------------------------------
@@ -325,6 +345,13 @@ class _LinearFn(torch.autograd.Function):
     def forward(ctx, x, w, b, route):
         ctx.save_for_backward(x, w)
         ctx.route = route
+        ctx.in_features = w.shape[1]
+        # BucketedDDP(direct_wgrad=True) offers a weight its gradient-bucket
+        # view through this attribute (parallel/ddp.py)
+        ctx.sink = getattr(w, "_sky_wgrad_sink", None)
+        # dy transposed, left here by the backward of a _SwiGLUFn that
+        # consumes this node's output (linear_swiglu)
+        ctx.dyT = None
         return torch.nn.functional.linear(x, w, b)
 
     @staticmethod
@@ -335,8 +362,18 @@ class _LinearFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = (dy2 @ w).view(x.shape)
         if ctx.needs_input_grad[1]:
+            dyT, ctx.dyT = ctx.dyT, None
+            # the step's first gradient of w goes straight into its bucket:
+            # no fresh dW and no add onto a zeroed bucket.  Any later one
+            # (gradient accumulation, a weight used twice) is returned and
+            # added by the DDP's hook as before.
+            out = ctx.sink.take() if ctx.sink is not None else None
             dw = native().linear_wgrad(dy2.contiguous(),
-                                       _rows(x).contiguous(), ctx.route)
+                                       _rows(x).contiguous(), ctx.route,
+                                       dyT=dyT, out=out)
+            if out is not None:
+                dw = None
+                ctx.sink.done()
         if ctx.needs_input_grad[2]:
             db = dy2.sum(0)
         return dx, dw, db, None
@@ -358,6 +395,19 @@ def linear(x, w, b=None, route: int = -1):
             return y
     _require_native("linear")
     return _LinearFn.apply(x, w, b, route)
+
+
+def linear_swiglu(x, w):
+    """swiglu(linear(x, w)): the gate|up projection and its activation, the
+    same two calls with the same values.  In the bf16 GPU backward, where
+    linear's weight gradient takes a route that wants dgu transposed, the
+    swiglu backward kernel writes that copy along with dgu (swiglu_bwd_t)
+    and linear_wgrad skips its transpose pass."""
+    gu = linear(x, w)
+    node = gu.grad_fn
+    if not isinstance(node, _LinearFn._backward_cls):
+        node = None
+    return _SwiGLUFn.apply(gu, node)
 
 
 class _QKVLinearFn(torch.autograd.Function):
@@ -1691,7 +1741,7 @@ def rope_kvwrite(qkv, kc, vc, cos, sin, positions, slot_ids, Hq, Hkv):
 
 __all__ = [
     "rmsnorm", "rope", "attention", "fused_cross_entropy", "attn_decode",
-    "swiglu", "linear", "qkv_linear",
+    "swiglu", "linear", "qkv_linear", "linear_swiglu",
     "decode_linear", "rmsnorm_res", "rope_kvwrite",
     "decode_swiglu_down",
     "native", "native_available", "rmsnorm_ref", "rope_ref",

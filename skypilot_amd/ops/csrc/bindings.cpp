@@ -89,6 +89,8 @@ void rope_kvwrite_launch(const void*, void*, void*, void*, const void*,
 void swiglu_fwd_launch(const void*, void*, long long, int, hipStream_t);
 void swiglu_bwd_launch(const void*, const void*, void*, long long, int,
                        hipStream_t);
+void swiglu_bwd_t_launch(const void*, const void*, void*, void*, int, int,
+                         hipStream_t);
 void skinny_gemm_fp8_norm_launch(const void*, const float*, const void*,
                                  const void*, const void*, void*, float,
                                  void*, int, int, int, hipStream_t);
@@ -1034,8 +1036,53 @@ std::vector<torch::Tensor> linear_wgrad_packed(std::vector<torch::Tensor> dys,
   return dWs;
 }
 
-torch::Tensor linear_wgrad(torch::Tensor dy, torch::Tensor x, int64_t route) {
-  return linear_wgrad_packed({dy}, x, route)[0];
+// One dy.  dyT, if given, is dy already transposed ([out, M], e.g. from
+// swiglu_bwd_t): routes 1 and 2 then skip their dy transpose; route 0 ignores
+// it.  out, if given, is where the final GEMM of the route writes dW (a
+// gradient-bucket view): the products are the ones formed without it
+// (at::linear(a, b) is mm(a, b.t())), so the bits are the same.
+torch::Tensor linear_wgrad(torch::Tensor dy, torch::Tensor x, int64_t route,
+                           c10::optional<torch::Tensor> dyT,
+                           c10::optional<torch::Tensor> out) {
+  if (!dyT.has_value() && !out.has_value())
+    return linear_wgrad_packed({dy}, x, route)[0];
+  const char* op = "linear_wgrad";
+  TORCH_CHECK(route >= -1 && route <= 2, op, ": route must be -1 (table), "
+              "0 (library), 1 (both transposed) or 2 (dy transposed), got ",
+              route);
+  check_dense(op, "x", x, at::kBFloat16, x);
+  TORCH_CHECK(x.dim() == 2, op, ": x must be [M, in], got ", x.sizes());
+  const int64_t M = x.size(0), in = x.size(1);
+  check_dense(op, "dy", dy, at::kBFloat16, x);
+  TORCH_CHECK(dy.dim() == 2 && dy.size(0) == M, op, ": dy must be [M = ", M,
+              ", out], got ", dy.sizes());
+  const int64_t outd = dy.size(1);
+  if (dyT.has_value()) {
+    check_dense(op, "dyT", *dyT, at::kBFloat16, x);
+    TORCH_CHECK(dyT->dim() == 2 && dyT->size(0) == outd && dyT->size(1) == M,
+                op, ": dyT must be [out = ", outd, ", M = ", M, "], got ",
+                dyT->sizes());
+  }
+  if (out.has_value()) {
+    check_dense(op, "out", *out, at::kBFloat16, x);
+    TORCH_CHECK(out->dim() == 2 && out->size(0) == outd && out->size(1) == in,
+                op, ": out must be [out = ", outd, ", in = ", in, "], got ",
+                out->sizes());
+  }
+  if (route < 0) route = wgrad_table_route(M, outd, in);
+  auto mm = [&](const torch::Tensor& a, const torch::Tensor& b) {
+    return out.has_value() ? at::mm_out(*out, a, b) : at::mm(a, b);
+  };
+  // the same rule as linear_wgrad_packed: off the 64-tile is the library's
+  if (route == 0 || !(transposable(x) && transposable(dy)))
+    return mm(dy.t(), x);
+  auto t = dyT.has_value() ? *dyT : transpose_bf16(dy);
+  return route == 1 ? mm(t, transpose_bf16(x).t()) : mm(t, x);
+}
+
+// The route linear_wgrad(route = -1) resolves for dy [M, out], x [M, in].
+int64_t wgrad_route(int64_t M, int64_t out, int64_t in) {
+  return wgrad_table_route(M, out, in);
 }
 
 torch::Tensor skinny_gemm_fp8(torch::Tensor X, torch::Tensor W8,
@@ -1645,6 +1692,33 @@ torch::Tensor swiglu_bwd(torch::Tensor gu, torch::Tensor dy) {
   return dgu;
 }
 
+// swiglu_bwd plus its transpose: (dgu [rows, 2M], dguT [2M, rows]) for 2-D
+// gu [rows, 2M] and dy [rows, M], rows and M multiples of 64 (the kernel
+// moves whole 64x64 tiles; other shapes raise).
+std::vector<torch::Tensor> swiglu_bwd_t(torch::Tensor gu, torch::Tensor dy) {
+  const char* op = "swiglu_bwd_t";
+  check_dense(op, "gu", gu, at::kBFloat16, gu);
+  check_dense(op, "dy", dy, at::kBFloat16, gu);
+  TORCH_CHECK(gu.dim() == 2 && dy.dim() == 2, op, ": gu and dy must be 2-D, "
+              "got ", gu.sizes(), " and ", dy.sizes());
+  const int64_t rows = gu.size(0), M = dy.size(1);
+  TORCH_CHECK(dy.size(0) == rows && gu.size(1) == 2 * M, op, ": gu must be "
+              "[rows, 2M] and dy [rows, M], got ", gu.sizes(), " and ",
+              dy.sizes());
+  TORCH_CHECK(rows > 0 && M > 0 && rows % 64 == 0 && M % 64 == 0 &&
+              rows <= std::numeric_limits<int>::max() &&
+              2 * M <= std::numeric_limits<int>::max(), op, ": rows and M "
+              "must be positive multiples of 64 (rows % 64, M % 64), got "
+              "rows = ", rows, ", M = ", M);
+  TORCH_CHECK(aligned16(gu) && aligned16(dy), op, ": gu and dy must start on "
+              "a 16-byte boundary");
+  auto dgu = torch::empty_like(gu);
+  auto dguT = torch::empty({2 * M, rows}, gu.options());
+  swiglu_bwd_t_launch(gu.data_ptr(), dy.data_ptr(), dgu.data_ptr(),
+                      dguT.data_ptr(), (int)rows, (int)M, cur_stream());
+  return {dgu, dguT};
+}
+
 // ---- MFMA layout probe (used by tests/test_gpu_mfma.py) -------------------
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B) {
   CHECK_GPU(A); CHECK_BF16(A); CHECK_CONTIG(A); CHECK_CONTIG(B);
@@ -1709,7 +1783,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_tn", &wgrad_tn);
   m.def("transpose_bf16_out", &transpose_bf16_out);
   m.def("linear_wgrad", &linear_wgrad, py::arg("dy"), py::arg("x"),
-        py::arg("route") = -1);
+        py::arg("route") = -1, py::arg("dyT") = py::none(),
+        py::arg("out") = py::none());
+  m.def("wgrad_route", &wgrad_route, py::arg("M"), py::arg("out"),
+        py::arg("in"));
   m.def("linear_wgrad_packed", &linear_wgrad_packed, py::arg("dys"),
         py::arg("x"), py::arg("route") = -1);
   m.def("adamw_step_mt", &adamw_step_mt);
@@ -1744,6 +1821,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_fp8_norm", &skinny_gemm_fp8_norm);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
+  m.def("swiglu_bwd_t", &swiglu_bwd_t, py::arg("gu"), py::arg("dy"));
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma32_probe", &mfma32_probe);
   m.def("trb16_probe", &trb16_probe);

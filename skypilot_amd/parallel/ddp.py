@@ -37,23 +37,69 @@ class GradBucket:
             off += p.numel()
         self.pending = 0
         self.work = None
+        # direct_wgrad bookkeeping (BucketedDDP): `zeroed` says zero_grad
+        # cleared flat for the current step; `fresh` holds the parameters
+        # with no gradient in flat yet this step; `counted` those whose
+        # gradient of the current backward is in; `direct` those whose first
+        # gradient of the step was written in place by its producer.
+        self.zeroed = True
+        self.fresh = set()
+        self.counted = set()
+        self.direct = set()
+
+
+class _WgradSink:
+    """What BucketedDDP(direct_wgrad=True) offers a weight as
+    ``p._sky_wgrad_sink``.  A backward that can write its weight gradient
+    anywhere (ops.linear) asks ``take()`` for the bucket view: it gets one
+    only for the step's first gradient of that parameter, writes dW into it,
+    returns no gradient to autograd and calls ``done()``, which does the
+    bookkeeping of the post-accumulate hook that then never runs."""
+
+    def __init__(self, ddp, p):
+        self.ddp, self.p = ddp, p
+
+    def take(self):
+        b = self.ddp._p2b[self.p]
+        if self.p not in b.fresh:
+            return None
+        b.fresh.discard(self.p)
+        b.direct.add(self.p)
+        return b.views[self.p]
+
+    def done(self):
+        self.ddp._grad_landed(self.p)
 
 
 class BucketedDDP:
     """Gradient-summing DDP with comm/compute overlap.
 
     Usage per step:
+        ddp.zero_grad(); then per micro-step
         ddp.mark_step_start(); loss.backward(); ddp.finish()
     After ``finish`` each param's gradient (summed over ranks) is in
     ``p._sky_grad``; divide-by-world is folded into the optimizer via
     ``ddp.grad_scale``.
+
+    ``direct_wgrad=True``: 2-D parameters that appear once in the model get
+    a ``_sky_wgrad_sink`` (_WgradSink), through which ops.linear's backward
+    writes the step's first weight gradient straight into the bucket view
+    instead of into a fresh tensor that the hook then adds onto zeros.  A
+    bucket all of whose parameters were written that way in the last step
+    is not zeroed for the next one; a parameter of such a bucket that is
+    not written in place after all has its first gradient copied rather
+    than added, or is zeroed in ``finish`` if it gets none.  The values are
+    those of the hook path, except that ``0 + g`` turns a ``-0`` into
+    ``+0`` and ``g`` alone does not.  ``False`` is the hook path for every
+    parameter.
     """
 
     def __init__(self, model: torch.nn.Module,
                  bucket_bytes: int = DEFAULT_BUCKET_BYTES,
-                 process_group=None):
+                 process_group=None, direct_wgrad: bool = True):
         self.model = model
         self.group = process_group
+        self.direct_wgrad = direct_wgrad
         self.world = dist.get_world_size(process_group) if _initialized() else 1
         params = [p for p in model.parameters() if p.requires_grad]
         # Reverse registration order approximates backward completion order,
@@ -69,12 +115,22 @@ class BucketedDDP:
                 cur, cur_bytes = [], 0
         if cur:
             self.buckets.append(GradBucket(cur, cur[0].device, cur[0].dtype))
+        # A tied parameter gets gradients from two layers in one backward:
+        # the second would be added after the sink counted the first, maybe
+        # after the bucket's all-reduce has started.  It stays on the hook.
+        uses = {}
+        for _, p in model.named_parameters(remove_duplicate=False):
+            uses[p] = uses.get(p, 0) + 1
         self._p2b = {}
         for b in self.buckets:
             for p in b.params:
                 self._p2b[p] = b
                 p._sky_grad = b.views[p]
                 p.register_post_accumulate_grad_hook(self._hook)
+                if direct_wgrad and p.dim() == 2 and uses.get(p, 0) == 1:
+                    p._sky_wgrad_sink = _WgradSink(self, p)
+                elif hasattr(p, "_sky_wgrad_sink"):
+                    del p._sky_wgrad_sink   # an earlier DDP's
         self._accumulating = False
         if self.world > 1:
             for p in model.parameters():
@@ -83,19 +139,36 @@ class BucketedDDP:
     def _rank0(self) -> int:
         return 0 if self.group is None else dist.get_global_rank(self.group, 0)
 
-    def _hook(self, p):
+    def _grad_landed(self, p):
+        """p's gradient of this backward is in its bucket."""
         b = self._p2b[p]
-        # Always accumulate: zero_grad() clears the flat buffers at the
-        # start of each optimizer step, so add_ is correct for both the
-        # single-micro-step case and every micro-step of grad accumulation.
-        # (copy_ on the final micro-step would overwrite the accumulated
-        # sum from earlier micro-steps.)
-        b.views[p].add_(p.grad)
-        p.grad = None  # free eagerly; flat buffer is the only grad storage
+        if p in b.counted:   # a second gradient in one backward
+            return
+        b.counted.add(p)
         b.pending -= 1
         if b.pending == 0 and self.world > 1 and not self._accumulating:
             b.work = dist.all_reduce(b.flat, op=dist.ReduceOp.SUM,
                                      group=self.group, async_op=True)
+
+    def _hook(self, p):
+        if p.grad is None:
+            # autograd still visits the parameter when its producer returned
+            # no gradient, having written it through the sink
+            return
+        b = self._p2b[p]
+        # Accumulate: zero_grad() clears the flat buffers at the start of
+        # each optimizer step, so add_ is correct for both the
+        # single-micro-step case and every micro-step of grad accumulation.
+        # (copy_ on the final micro-step would overwrite the accumulated
+        # sum from earlier micro-steps.)  Only the step's first gradient
+        # into a bucket that zero_grad() skipped is copied.
+        if p in b.fresh and not b.zeroed:
+            b.views[p].copy_(p.grad)
+        else:
+            b.views[p].add_(p.grad)
+        b.fresh.discard(p)
+        p.grad = None  # free eagerly; flat buffer is the only grad storage
+        self._grad_landed(p)
 
     def mark_step_start(self, accumulating: bool = False):
         """Call before each backward. ``accumulating=True`` defers the
@@ -103,15 +176,29 @@ class BucketedDDP:
         self._accumulating = accumulating
         for b in self.buckets:
             b.pending = len(b.params)
+            b.counted.clear()
             b.work = None
 
     def zero_grad(self):
         for b in self.buckets:
-            b.flat.zero_()
+            # every parameter written in place last step: expect the same
+            # again and leave the old values to be overwritten
+            b.zeroed = not (self.direct_wgrad
+                            and len(b.direct) == len(b.params))
+            if b.zeroed:
+                b.flat.zero_()
+            b.fresh = set(b.params)
+            b.direct.clear()
 
     def finish(self):
         """Wait for outstanding bucket reductions (call after backward)."""
         for b in self.buckets:
+            if not b.zeroed and b.fresh and not self._accumulating:
+                # the expectation failed: no gradient this step after all
+                assert b.work is None
+                for p in b.fresh:
+                    b.views[p].zero_()
+                b.fresh.clear()
             if b.work is not None:
                 b.work.wait()
             elif self.world > 1 and not self._accumulating:

@@ -35,6 +35,9 @@ class TrainConfig:
     warmup_steps: int = 0        # linear LR warmup
     lr_decay_steps: int = 0      # cosine decay horizon (0 = constant)
     min_lr_ratio: float = 0.1
+    # weight gradients of ops.linear written straight into the DDP's
+    # gradient buckets (BucketedDDP); False keeps every one on the hook
+    direct_wgrad: bool = True
 
 
 def dist_env():
@@ -90,7 +93,8 @@ class Trainer:
                                      dtype=torch.bfloat16, seed=cfg.seed)
         self.ddp = BucketedDDP(self.model,
                                bucket_bytes=cfg.bucket_mb << 20,
-                               process_group=self.dp_group)
+                               process_group=self.dp_group,
+                               direct_wgrad=cfg.direct_wgrad)
         self.opt = FusedAdamW(self.model.parameters(), lr=cfg.lr,
                               weight_decay=cfg.weight_decay)
         self.step_count = 0
